@@ -1,6 +1,7 @@
 """Benchmark: RAFT inference image-pairs/s on MI355X (BASELINE.json config 2).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]     (N > 1: spawns one rank per GPU itself)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+                                                            (N > 1: spawns one rank per GPU itself)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N   (one rank per GPU)
 
 A step = one RAFT-full forward (random-init weights, seeded) over one batch of
@@ -10,7 +11,13 @@ as one hipGraph.  Each rank processes its own batch (frame pairs shard across
 GPUs with no data-path collective; weights are broadcast once over RCCL), so
 scaling is weak.  Rank 0 prints one JSON line.
 
-The line also carries
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value,
+unit, ms_per_step, dtype, config ...) and nothing else.  --dump-outputs DIR also writes what the
+last timed step computed (rank 0's flow_low and flow_up, as plan.outputs() hands them to a
+caller) to DIR/flow_low.npy and DIR/flow_up.npy in float32; the inputs are seeded, so two builds
+run with the same arguments can be compared output for output.
+
+With --full the line also carries
   roofline      the forward's own lookup launch (the metric's "corr-lookup GB/s vs HBM
                 peak"): with the all-pairs RAFT-full loop that is raft_corr_lookup_conv
                 (the window lookup fused with the motion encoder's convc1 and convf1:
@@ -307,6 +314,28 @@ def cpu_baseline(args, budget_s=12.0):
                       f"container), torch.set_num_threads({threads}), {dt:.1f} s"}
 
 
+DUMP_LIMIT_BYTES = 60 * 10 ** 6  # of array data in one --dump-outputs directory (under 64 MB with the headers)
+
+
+def dump_outputs(dirname, tensors):
+    """--dump-outputs: write {name: device tensor} as dirname/<name>.npy in float32.  Whole arrays
+    while they fit DUMP_LIMIT_BYTES together; otherwise each array's share of the limit as a flat
+    sample at sorted element indices drawn from a PCG64 stream seeded by the array's name and size
+    (the same indices in every run and every build, so samples compare element for element)."""
+    import zlib
+
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    total = sum(t.numel() * 4 for t in tensors.values())
+    for name, t in tensors.items():
+        a = t.detach().to(torch.float32).cpu().numpy()
+        if total > DUMP_LIMIT_BYTES:
+            keep = max(1, a.size * DUMP_LIMIT_BYTES // total)
+            rng = np.random.Generator(np.random.PCG64([zlib.crc32(name.encode()), a.size]))
+            a = a.reshape(-1)[np.sort(rng.integers(0, a.size, keep))]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def spawn_ranks(n):
     """`bench.py --gpus N` (N > 1) without a launcher: start N rank processes of this script, rank r on
     cuda:r (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in their environment, as torch.distributed.run
@@ -355,9 +384,14 @@ def main():
     ap.add_argument("--width", type=int, default=1024)
     ap.add_argument("--iters", type=int, default=32)
     ap.add_argument("--alternate-corr", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rank 0) as DIR/flow_low.npy and DIR/flow_up.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the per-kernel / roofline figures, the RAFT.forward() path, the exact-f32 "
+                         "run and the CPU baseline (see the module docstring)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-fp32-exact", action="store_true", help="skip the exact-f32 comparison run")
+    ap.add_argument("--no-fp32-exact", action="store_true", help="with --full: skip the exact-f32 comparison run")
     ap.add_argument("--precision", choices=["fp32", "f16x3", "f16", "bf16"], default=None,
                     help="conv arithmetic (default: the RAFT default, f16x3)")
     args = ap.parse_args()
@@ -434,16 +468,43 @@ def main():
         return time.perf_counter() - t0
 
     elapsed = timed(plan, world > 1)
+    # what the last timed step computed, before anything else touches the plan's buffers
+    last = plan.outputs() if args.dump_outputs and rank == 0 else None
     if world > 1:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     pairs = world * args.batch * args.steps
     value = pairs / elapsed
-    if rank != 0:  # the per-kernel figures and the JSON line are rank 0's
+    if rank != 0:  # the outputs, the per-kernel figures and the JSON line are rank 0's
         dist.destroy_process_group()
         return
+    if last is not None:
+        dump_outputs(args.dump_outputs, dict(zip(("flow_low", "flow_up"), last)))
+        del last
 
+    out = {
+        "metric": "image-pairs/s at Sintel 436x1024, 32 iters; corr-lookup GB/s vs HBM peak",
+        "value": round(value, 3), "unit": "image-pairs/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": DTYPE[prec],
+        "data": "synthetic (seeded uint8-valued frames, random-init seeded weights)",
+        "config": {"workload": f"RAFT-full inference, {args.height}x{args.width} padded to {H}x{W}, "
+                               f"{args.batch} pair(s)/GPU/step, iters={args.iters}, "
+                               f"{'alternate' if args.alternate_corr else 'all-pairs'} corr, "
+                               f"{'eager' if args.no_graph else 'hipGraph'}",
+                   "global_batch": world * args.batch, "parallelism": f"frame-pair sharding x{world}"},
+    }
+    if args.full:
+        out.update(full_figures(args, model, plan, pool, timed, world, dev, H, W, prec))
+    print(json.dumps(out), flush=True)
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def full_figures(args, model, plan, pool, timed, world, dev, H, W, prec):
+    """The --full legs (rank 0, after the timed steps): the keys the module docstring lists, each
+    measured in runs of its own on the same model, plan and frame pool."""
     # ---- per-kernel live timing (HIP events on the launch stream, hipGraph replays) ----------
     from raft_optical_flow_amd import kernels as K
     h8, w8 = H // 8, W // 8
@@ -630,34 +691,12 @@ def main():
         model.conv_precision = args.precision
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args)
 
-    if rank == 0:
-        out = {
-            "metric": "image-pairs/s at Sintel 436x1024, 32 iters; corr-lookup GB/s vs HBM peak",
-            "value": round(value, 3), "unit": "image-pairs/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": DTYPE[prec],
-            "data": "synthetic (seeded uint8-valued frames, random-init seeded weights)",
-            "config": {"workload": f"RAFT-full inference, {args.height}x{args.width} padded to {H}x{W}, "
-                                   f"{args.batch} pair(s)/GPU/step, iters={args.iters}, "
-                                   f"{'alternate' if args.alternate_corr else 'all-pairs'} corr, "
-                                   f"{'eager' if args.no_graph else 'hipGraph'}",
-                       "global_batch": world * args.batch, "parallelism": f"frame-pair sharding x{world}"},
-            "roofline": roof,
-            "lookup_b1": lookup_b1,
-            "lookup_b8": lookup_b8,
-            "iteration": iteration,
-            "update_gemm": update_roof,
-            "dominant_kernel": dominant,
-            "drop_in_forward": drop_in,
-            "fp32_exact": exact,
-            "cpu_baseline": cpu,
-        }
-        print(json.dumps(out), flush=True)
-    if world > 1:
-        dist.destroy_process_group()
+    return {"roofline": roof, "lookup_b1": lookup_b1, "lookup_b8": lookup_b8, "iteration": iteration,
+            "update_gemm": update_roof, "dominant_kernel": dominant, "drop_in_forward": drop_in,
+            "fp32_exact": exact, "cpu_baseline": cpu}
 
 
 if __name__ == "__main__":

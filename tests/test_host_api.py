@@ -138,6 +138,28 @@ def test_bench_refuses_more_gpus_than_visible():
     assert r.returncode != 0 and "WORLD_SIZE=2 but --gpus 3" in r.stderr
 
 
+def test_bench_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """bench.py --dump-outputs writes float32 .npy files: whole arrays under the size limit, above it
+    the same seeded flat sample in every run, within the limit in total."""
+    import bench
+    g = torch.Generator().manual_seed(0)
+    t = {"flow_low": torch.randn(1, 2, 5, 7, generator=g), "flow_up": torch.randn(1, 2, 40, 56, generator=g)}
+    bench.dump_outputs(str(tmp_path / "whole"), t)
+    for k, v in t.items():
+        a = np.load(tmp_path / "whole" / f"{k}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, v.numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4000)
+    bench.dump_outputs(str(tmp_path / "s1"), t)
+    bench.dump_outputs(str(tmp_path / "s2"), {k: v.clone() for k, v in t.items()})
+    total = 0
+    for k, v in t.items():
+        a, b = np.load(tmp_path / "s1" / f"{k}.npy"), np.load(tmp_path / "s2" / f"{k}.npy")
+        assert a.dtype == np.float32 and a.ndim == 1 and 0 < a.size < v.numel() and np.array_equal(a, b)
+        assert np.isin(a, v.numpy()).all()
+        total += a.nbytes
+    assert 3000 < total <= 4000
+
+
 class _FakePlan:
     def __init__(self):
         self.released = False

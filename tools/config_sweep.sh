@@ -5,12 +5,13 @@
 set -o pipefail
 cd "$(dirname "$0")/.."
 TAG=${1:-sweep}
-OUT=gpurun_out/sweep_$TAG.jsonl
-mkdir -p gpurun_out
+export OUT_DIR=${OUT_DIR:-bench_out}
+OUT=$OUT_DIR/sweep_$TAG.jsonl
+mkdir -p $OUT_DIR
 : > $OUT
 run() {
   echo "== $*" >&2
-  timeout -k 10 300 python bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-fp32-exact "$@" >> $OUT 2>> gpurun_out/sweep_$TAG.err || { echo "failed: $*"; tail -20 gpurun_out/sweep_$TAG.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-fp32-exact "$@" >> $OUT 2>> $OUT_DIR/sweep_$TAG.err || { echo "failed: $*"; tail -20 $OUT_DIR/sweep_$TAG.err; exit 1; }
   tail -1 $OUT
 }
 run --batch 8 --alternate-corr                                   # config 3

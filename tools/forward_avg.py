@@ -1,5 +1,5 @@
 """Per-dispatch averages of bench.py's roofline kernels from a rocprofv3 kernel trace of the same
-bench command, to check bench.py's live figures against rocprof:
+bench command (`python bench.py --full`), to check bench.py's live figures against rocprof:
 
   * corr_lookup_kernel<4,4,false>, B=1 grid (1760 x 256 threads) and B=8 grid (14080 x 256), split into
       - rotated: the dispatches of bench.py's cache-cold rotation graphs (runs of >= 16 consecutive

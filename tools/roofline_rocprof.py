@@ -1,5 +1,5 @@
 """The bench's roofline launch under rocprof: splits the dispatches of one kernel in a
-rocprofv3 kernel trace of `python bench.py` into the back-to-back ones (the bench's own roofline
+rocprofv3 kernel trace of `python bench.py --full` into the back-to-back ones (the bench's own roofline
 graph: 4 x 32 launches of the forward's fused lookup with nothing between them) and the rest (the
 forwards), and prints their means next to the bench line's live figure.
 
