@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-#define RAFT_HIP_ABI_VERSION 18
+#define RAFT_HIP_ABI_VERSION 19
 
 /* Negative return codes (argument errors, raised before any launch). */
 #define RAFT_E_INVALID (-1)   /* bad size / null pointer / unsupported shape */
@@ -365,6 +365,32 @@ int raft_conv2d_halo_tile_rows(const raft_conv2d_params* p);
  * ceil(tiles / CUs) for a launch of more tiles than CUs: the loaders run on into the next tile while
  * the compute waves store the last one), 0 when the halo kernel does not run it (inspection / tests). */
 int raft_conv2d_halo_tiles_per_wg(const raft_conv2d_params* p);
+/* The kernel form raft_conv2d launches for a conv (inspection / tests; since ABI 19).  The query runs
+ * the launch's own decision code up to the point of the launch and records the instantiation it
+ * would start instead of starting it: nothing is launched and no operand is dereferenced (the
+ * pointers only have to pass raft_conv2d's argument checks), so it runs without a device (the tile
+ * rules then assume 256 CUs).  Fields a kernel does not have are 0. */
+#define RAFT_CONV_KERNEL_HALO 1       /* conv_halo: stride-1 "same" 1x1 / 3x3 / 1x5 / 5x1, split precisions */
+#define RAFT_CONV_KERNEL_GEMM 2       /* conv_gemm: 64 x 64 implicit-GEMM tiles (everything else) */
+#define RAFT_CONV_KERNEL_STEM 3       /* conv_stem: the encoders' 7x7 / stride-2 stem */
+#define RAFT_CONV_KERNEL_SMALLN 4     /* N <= 4 on the VALU, any geometry */
+#define RAFT_CONV_KERNEL_SMALLN3X3 5  /* N <= 2 stride-1 3x3 on the VALU (LDS row tiles) */
+struct raft_conv2d_form {     /* (no typedef: the query below has the same name; say `struct raft_conv2d_form`) */
+  int kernel;                  /* RAFT_CONV_KERNEL_* */
+  int tile_rows;               /* halo: image rows of a spatial tile, 8 or 16 */
+  int tile_cols;               /* halo: output channels of a tile, 32 / 64 / 128 */
+  int tiles_per_wg;            /* halo: spatial tiles a work-group runs back to back */
+  int loader_waves;            /* halo: 4 or 8 */
+  int compute_waves_per_simd;  /* halo: 1, or 2 for the K-split form (raft_conv2d_set_halo_ks) */
+  int gemm_k_groups;           /* gemm: 1 or 2 K-groups per tile */
+  int smalln_tile_rows;        /* smalln3x3: 2 or 4 image rows per tile */
+};
+/* 0 and *out filled, or raft_conv2d's argument error for these params (out untouched). */
+int raft_conv2d_form(const raft_conv2d_params* p, struct raft_conv2d_form* out);
+/* The same for raft_conv2d_pair(p0, p1): *one_launch = 1 when the two share one halo launch (out[0]
+ * and out[1] then describe that launch), 0 when they run in order (each as raft_conv2d_form). */
+int raft_conv2d_pair_form(const raft_conv2d_params* p0, const raft_conv2d_params* p1,
+                          struct raft_conv2d_form out[2], int* one_launch);
 /* 1 when the conv can apply its input's InstanceNorm in its loaders (in_norm above: the halo
  * kernel's 3x3 convs over <= 256 channels), else 0. */
 int raft_conv2d_in_norm_ok(const raft_conv2d_params* p);

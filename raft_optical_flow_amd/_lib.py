@@ -29,7 +29,7 @@ PREC_F16 = 2     # single f16 product (mixed precision)
 PREC_BF16 = 3    # single bf16 product on v_mfma_f32_32x32x16_bf16 (bf16 mixed precision)
 PRECISIONS = {"fp32": PREC_FP32, "f16x3": PREC_F16X3, "f16": PREC_F16, "bf16": PREC_BF16}
 
-ABI_VERSION = 18
+ABI_VERSION = 19
 RANGE_LIMIT = 32768.0  # RAFT_RANGE_LIMIT: |x| above it raises the f16x3 range guard
 
 EPI_LINEAR = 0
@@ -65,6 +65,41 @@ class ConvParams(ctypes.Structure):
         ("in_norm", P), ("in_norm_relu", c_int),
         ("weight_s", P),
     ]
+
+
+CONV_KERNEL_HALO = 1
+CONV_KERNEL_GEMM = 2
+CONV_KERNEL_STEM = 3
+CONV_KERNEL_SMALLN = 4
+CONV_KERNEL_SMALLN3X3 = 5
+
+
+class ConvForm(ctypes.Structure):
+    """Mirror of `struct raft_conv2d_form` (include/raft_hip.h): the kernel form a conv launches."""
+
+    _fields_ = [
+        ("kernel", c_int), ("tile_rows", c_int), ("tile_cols", c_int), ("tiles_per_wg", c_int),
+        ("loader_waves", c_int), ("compute_waves_per_simd", c_int), ("gemm_k_groups", c_int),
+        ("smalln_tile_rows", c_int),
+    ]
+
+    def astuple(self):
+        return tuple(getattr(self, f) for f, _ in self._fields_)
+
+
+def conv_form(p: ConvParams) -> ConvForm:
+    """raft_conv2d_form of p (host only: nothing is launched)."""
+    f = ConvForm()
+    call("raft_conv2d_form", ctypes.byref(p), ctypes.byref(f))
+    return f
+
+
+def conv_pair_form(p0: ConvParams, p1: ConvParams):
+    """raft_conv2d_pair_form: (form of p0, form of p1, one_launch)."""
+    f = (ConvForm * 2)()
+    one = c_int(0)
+    call("raft_conv2d_pair_form", ctypes.byref(p0), ctypes.byref(p1), f, ctypes.byref(one))
+    return f[0], f[1], bool(one.value)
 
 
 # name -> (restype, argtypes)
@@ -111,6 +146,9 @@ _PROTOS = {
     "raft_conv2d_stats_slots": (c_int, [ctypes.POINTER(ConvParams)]),
     "raft_conv2d_halo_tile_rows": (c_int, [ctypes.POINTER(ConvParams)]),
     "raft_conv2d_halo_tiles_per_wg": (c_int, [ctypes.POINTER(ConvParams)]),
+    "raft_conv2d_form": (c_int, [ctypes.POINTER(ConvParams), ctypes.POINTER(ConvForm)]),
+    "raft_conv2d_pair_form": (c_int, [ctypes.POINTER(ConvParams), ctypes.POINTER(ConvParams),
+                                      ctypes.POINTER(ConvForm), ctypes.POINTER(c_int)]),
     "raft_debug_launch_span": (c_int, [c_int]),
     "raft_debug_launch_span_read": (c_int, [P, c_int]),
     "raft_conv2d_in_norm_ok": (c_int, [ctypes.POINTER(ConvParams)]),

@@ -388,13 +388,18 @@ struct HaloOperands {
   unsigned w_bytes, in0_bytes, in1_bytes;
 };
 
+// (the C header gives the struct and its query function one name: the type needs its tag keyword)
+using ConvForm = struct raft_conv2d_form;
+
 // conv_halo.hip: the halo-tiled LDS-DMA kernel for stride-1 "same" convs;
 // returns 1 (nothing launched) when the conv is not one it covers
-int conv_halo_launch(const HaloOperands& o, hipStream_t s);
+// (all three: with form != nullptr the call is raft_conv2d_form's query -- the same decisions, the form
+// of the launch written to *form (the pair: form[0] and form[1]) and nothing launched)
+int conv_halo_launch(const HaloOperands& o, hipStream_t s, ConvForm* form = nullptr);
 // two independent convs of one shape class in one launch; 1 (nothing launched) if they do not qualify
-int conv_halo_launch_pair(const HaloOperands& o0, const HaloOperands& o1, hipStream_t s);
+int conv_halo_launch_pair(const HaloOperands& o0, const HaloOperands& o1, hipStream_t s, ConvForm* form = nullptr);
 // conv_stem.hip: the encoders' 7x7 / stride-2 stem over 3 channels; 1 (nothing launched) otherwise
-int conv_stem_launch(const raft_conv2d_params& p, int k_pad, hipStream_t s);
+int conv_stem_launch(const raft_conv2d_params& p, int k_pad, hipStream_t s, ConvForm* form = nullptr);
 // tile-statistics slots per image of a conv on the halo / stem kernel (raft_conv2d_stats_slots), 0 if none
 int conv_halo_stats_slots(const HaloOperands& o);
 // whether conv_halo_launch takes the conv

@@ -954,7 +954,10 @@ bool reads_output_of(const raft_conv2d_params& y, const raft_conv2d_params& x) {
 }
 }  // namespace
 
-extern "C" int raft_conv2d(const raft_conv2d_params* pp, raft_stream_t stream) {
+namespace {
+// raft_conv2d, and with q != nullptr raft_conv2d_form: the same checks and the same kernel choice, but
+// the form of the launch is written to *q and nothing is launched (no second copy of the rules)
+int conv_dispatch(const raft_conv2d_params* pp, raft_stream_t stream, ConvForm* q) {
   ConvArgs a;
   HaloOperands o;
   const int rc = conv_prepare(pp, a, o);
@@ -971,13 +974,25 @@ extern "C" int raft_conv2d(const raft_conv2d_params* pp, raft_stream_t stream) {
         const char* e = getenv("RAFT_SN_TH4_MIN");
         return e ? atol(e) : (long)SN_TH4_MIN_TILES;
       }();
-      if (t4 >= th4_min) {
+      const int sn_th = t4 >= th4_min ? 4 : 2;
+      if (q) {
+        *q = ConvForm{};
+        q->kernel = RAFT_CONV_KERNEL_SMALLN3X3;
+        q->smalln_tile_rows = sn_th;
+        return 0;
+      }
+      if (sn_th == 4) {
         hipLaunchKernelGGL((conv_smalln3x3_kernel<2, 4>), dim3((unsigned)t4), dim3(512), 0, s, a, p.weight);
       } else {
         const long t2 = (long)p.batch * cdiv(p.out_h, 2) * cdiv(p.out_w, 16);
         hipLaunchKernelGGL((conv_smalln3x3_kernel<2, 2>), dim3((unsigned)t2), dim3(512), 0, s, a, p.weight);
       }
       return check_launch("raft_conv2d(small n 3x3)");
+    }
+    if (q) {
+      *q = ConvForm{};
+      q->kernel = RAFT_CONV_KERNEL_SMALLN;
+      return 0;
     }
     dim3 grid((unsigned)cdiv_l(a.M, 4));
     if (p.n <= 2)
@@ -994,8 +1009,8 @@ extern "C" int raft_conv2d(const raft_conv2d_params* pp, raft_stream_t stream) {
     RAFT_REQUIRE(p.stats_ld >= p.n && ((uintptr_t)p.stats_part & 15) == 0,
                  "raft_conv2d: stats_ld >= n and a 16-B aligned stats_part");
   }
-  if (p.mode == RAFT_CONV_VEC && conv_halo_launch(o, s) == 0) return check_launch("raft_conv2d(halo)");
-  if (p.mode == RAFT_CONV_GATHER && conv_stem_launch(p, o.k_pad, s) == 0) return check_launch("raft_conv2d(stem)");
+  if (p.mode == RAFT_CONV_VEC && conv_halo_launch(o, s, q) == 0) return q ? 0 : check_launch("raft_conv2d(halo)");
+  if (p.mode == RAFT_CONV_GATHER && conv_stem_launch(p, o.k_pad, s, q) == 0) return q ? 0 : check_launch("raft_conv2d(stem)");
   a.gn = n_pad / BN;
   a.hw = p.out_h * p.out_w;
   a.tpi = p.stats_part ? cdiv(a.hw, BM) : 0;
@@ -1004,8 +1019,27 @@ extern "C" int raft_conv2d(const raft_conv2d_params* pp, raft_stream_t stream) {
   dim3 grid((unsigned)tiles);
   // few tiles (fewer than ~4 per CU): two K-groups per tile give every SIMD two waves
   const bool two = tiles < 1024 && a.K / BK >= 4;
+  if (q) {
+    *q = ConvForm{};
+    q->kernel = RAFT_CONV_KERNEL_GEMM;
+    q->gemm_k_groups = two ? 2 : 1;
+    return 0;
+  }
   launch_gemm(a, grid, two, s);
   return check_launch("raft_conv2d");
+}
+}  // namespace
+
+extern "C" int raft_conv2d(const raft_conv2d_params* pp, raft_stream_t stream) {
+  return conv_dispatch(pp, stream, nullptr);
+}
+
+extern "C" int raft_conv2d_form(const raft_conv2d_params* pp, ConvForm* out) {
+  RAFT_REQUIRE(out != nullptr, "raft_conv2d_form: null out");
+  ConvForm f;
+  const int rc = conv_dispatch(pp, nullptr, &f);
+  if (rc == 0) *out = f;
+  return rc;
 }
 
 extern "C" int raft_conv2d_in_norm_ok(const raft_conv2d_params* pp) {
@@ -1051,7 +1085,10 @@ extern "C" int raft_conv2d_stats_slots(const raft_conv2d_params* pp) {
   return conv_stem_stats_slots(p, o.k_pad);
 }
 
-extern "C" int raft_conv2d_pair(const raft_conv2d_params* p0, const raft_conv2d_params* p1, raft_stream_t stream) {
+namespace {
+// raft_conv2d_pair, and with q != nullptr raft_conv2d_pair_form (as conv_dispatch)
+int conv_pair_dispatch(const raft_conv2d_params* p0, const raft_conv2d_params* p1, raft_stream_t stream,
+                       ConvForm* q, int* one_launch) {
   ConvArgs a0, a1;
   HaloOperands o0, o1;
   int rc = conv_prepare(p0, a0, o0);
@@ -1063,9 +1100,31 @@ extern "C" int raft_conv2d_pair(const raft_conv2d_params* p0, const raft_conv2d_
   // one launch only when neither reads what the other writes and no element is written by both
   // (otherwise: in order, as two calls)
   const bool independent = !reads_output_of(*p1, *p0) && !reads_output_of(*p0, *p1) && !writes_overlap(*p0, *p1);
-  if (independent && !small_n(*p0) && !small_n(*p1) && conv_halo_launch_pair(o0, o1, as_stream(stream)) == 0)
-    return check_launch("raft_conv2d_pair(halo)");
-  rc = raft_conv2d(p0, stream);
+  if (independent && !small_n(*p0) && !small_n(*p1) && conv_halo_launch_pair(o0, o1, as_stream(stream), q) == 0) {
+    if (one_launch) *one_launch = 1;
+    return q ? 0 : check_launch("raft_conv2d_pair(halo)");
+  }
+  if (one_launch) *one_launch = 0;
+  rc = conv_dispatch(p0, stream, q);
   if (rc) return rc;
-  return raft_conv2d(p1, stream);
+  return conv_dispatch(p1, stream, q ? q + 1 : nullptr);
+}
+}  // namespace
+
+extern "C" int raft_conv2d_pair(const raft_conv2d_params* p0, const raft_conv2d_params* p1, raft_stream_t stream) {
+  return conv_pair_dispatch(p0, p1, stream, nullptr, nullptr);
+}
+
+extern "C" int raft_conv2d_pair_form(const raft_conv2d_params* p0, const raft_conv2d_params* p1, ConvForm out[2],
+                                     int* one_launch) {
+  RAFT_REQUIRE(out != nullptr && one_launch != nullptr, "raft_conv2d_pair_form: null out / one_launch");
+  ConvForm f[2];
+  int one = 0;
+  const int rc = conv_pair_dispatch(p0, p1, nullptr, f, &one);
+  if (rc == 0) {
+    out[0] = f[0];
+    out[1] = f[1];
+    *one_launch = one;
+  }
+  return rc;
 }

@@ -1319,8 +1319,26 @@ bool halo_nl8_enc() {
 // them, and the launch refuses m > 1 (the one-tile kernel would run only 1/m of the spatial tiles)
 constexpr bool halo_no_mt(int prec, int taps, int bn) { return prec != RAFT_PREC_F16X3 && taps == 9 && bn == 128; }
 
+// The last step of every halo launch: starts the chosen instantiation, or (the form query,
+// raft_conv2d_form: q != nullptr) writes its description to *q and starts nothing.  The launch and the
+// query run the same launch_halo* code down to this call, so what the query reports is what a launch runs.
+template <int KH, int KW, int BNT, int PREC, bool ENC, int TH, bool MT, int NL = 4, int KS = 1>
+void halo_start(const HaloLaunch& l, dim3 grid, hipStream_t s, ConvForm* q) {
+  if (q) {
+    *q = ConvForm{};
+    q->kernel = RAFT_CONV_KERNEL_HALO;
+    q->tile_rows = TH;
+    q->tile_cols = BNT;
+    q->tiles_per_wg = MT ? l.m : 1;
+    q->loader_waves = NL;
+    q->compute_waves_per_simd = KS;
+    return;
+  }
+  hipLaunchKernelGGL((conv_halo_kernel<KH, KW, BNT, PREC, ENC, TH, MT, NL, KS>), grid, dim3(64 * (4 * KS + NL)), 0, s, l);
+}
+
 template <int KH, int KW, int BNT, int PREC, bool ENC = false, int TH = HTH>
-void launch_halo_mt(const HaloLaunch& l, dim3 grid, hipStream_t s) {
+void launch_halo_mt(const HaloLaunch& l, dim3 grid, hipStream_t s, ConvForm* q) {
   constexpr bool NO_MT = halo_no_mt(PREC, KH * KW, BNT);
   if (NO_MT && l.m > 1) {
     fprintf(stderr, "raft_hip: internal error: a one-tile-only halo conv was planned with %d tiles per work-group\n", l.m);
@@ -1334,9 +1352,9 @@ void launch_halo_mt(const HaloLaunch& l, dim3 grid, hipStream_t s) {
   if constexpr (CAN_NL8E) {
     if (halo_nl8_enc()) {
       if (l.m > 1)
-        hipLaunchKernelGGL((conv_halo_kernel<KH, KW, BNT, PREC, ENC, TH, true, 8>), grid, dim3(768), 0, s, l);
+        halo_start<KH, KW, BNT, PREC, ENC, TH, true, 8>(l, grid, s, q);
       else
-        hipLaunchKernelGGL((conv_halo_kernel<KH, KW, BNT, PREC, ENC, TH, false, 8>), grid, dim3(768), 0, s, l);
+        halo_start<KH, KW, BNT, PREC, ENC, TH, false, 8>(l, grid, s, q);
       return;
     }
   }
@@ -1344,37 +1362,37 @@ void launch_halo_mt(const HaloLaunch& l, dim3 grid, hipStream_t s) {
   constexpr bool CAN_KS2 = CAN_NL8 && (BNT == 64 || (BNT == 32 && HALO_KS2_BN32)) &&
                            HaloCfg<KH, KW, BNT, 128, TH>::D == 3 && !HALO_NOLSPLIT;
   if (!NO_MT && l.m > 1) {
-    hipLaunchKernelGGL((conv_halo_kernel<KH, KW, BNT, PREC, ENC, TH, !NO_MT>), grid, dim3(512), 0, s, l);
+    halo_start<KH, KW, BNT, PREC, ENC, TH, !NO_MT>(l, grid, s, q);
   } else {
     if constexpr (CAN_KS2) {
       if (halo_ks2()) {
 #if HALO_KS2_NL8  // dev builds: 8 loaders beside the 8 compute waves (1024 threads, 128 VGPRs per wave)
-        hipLaunchKernelGGL((conv_halo_kernel<KH, KW, BNT, PREC, ENC, TH, false, 8, 2>), grid, dim3(1024), 0, s, l);
+        halo_start<KH, KW, BNT, PREC, ENC, TH, false, 8, 2>(l, grid, s, q);
 #else
-        hipLaunchKernelGGL((conv_halo_kernel<KH, KW, BNT, PREC, ENC, TH, false, 4, 2>), grid, dim3(768), 0, s, l);
+        halo_start<KH, KW, BNT, PREC, ENC, TH, false, 4, 2>(l, grid, s, q);
 #endif
         return;
       }
     }
     if constexpr (CAN_NL8) {
       if (halo_nl8()) {
-        hipLaunchKernelGGL((conv_halo_kernel<KH, KW, BNT, PREC, ENC, TH, false, 8>), grid, dim3(768), 0, s, l);
+        halo_start<KH, KW, BNT, PREC, ENC, TH, false, 8>(l, grid, s, q);
         return;
       }
     }
-    hipLaunchKernelGGL((conv_halo_kernel<KH, KW, BNT, PREC, ENC, TH, false>), grid, dim3(512), 0, s, l);
+    halo_start<KH, KW, BNT, PREC, ENC, TH, false>(l, grid, s, q);
   }
 }
 
 template <int KH, int KW, int PREC>
-void launch_halo_p(const HaloLaunch& l, int bn, int th, dim3 grid, hipStream_t s) {
+void launch_halo_p(const HaloLaunch& l, int bn, int th, dim3 grid, hipStream_t s, ConvForm* q) {
   const raft_conv2d_params& p = l.a[0].p;
   if constexpr (KH == 3 && KW == 3) {
     if (th == HTH_BIG) {  // (halo_pick: N tile 64)
       if (p.stats_part || p.in_norm)
-        launch_halo_mt<3, 3, 64, PREC, true, HTH_BIG>(l, grid, s);
+        launch_halo_mt<3, 3, 64, PREC, true, HTH_BIG>(l, grid, s, q);
       else
-        launch_halo_mt<3, 3, 64, PREC, false, HTH_BIG>(l, grid, s);
+        launch_halo_mt<3, 3, 64, PREC, false, HTH_BIG>(l, grid, s, q);
       return;
     }
   } else if constexpr (KH * KW == 5) {
@@ -1382,39 +1400,39 @@ void launch_halo_p(const HaloLaunch& l, int bn, int th, dim3 grid, hipStream_t s
     // 16 x 20 patches the T = 5 ring needs (D = 3); f16x3's 128-B rows do not, so it runs D = 2 with
     // fp32 patches split by the compute waves (216 / 232 VGPRs)
     if (th == HTH_BIG) {
-      launch_halo_mt<KH, KW, 64, PREC, false, HTH_BIG>(l, grid, s);
+      launch_halo_mt<KH, KW, 64, PREC, false, HTH_BIG>(l, grid, s, q);
       return;
     }
   }
   if constexpr (PREC != RAFT_PREC_F16X3) {
     if (bn == 128) {  // (conv_halo_launch picks it only without stats_part / in_norm)
-      launch_halo_mt<KH, KW, 128, PREC>(l, grid, s);
+      launch_halo_mt<KH, KW, 128, PREC>(l, grid, s, q);
       return;
     }
   }
   if constexpr ((KH == 1 && KW == 1) || (KH == 3 && KW == 3)) {
     if (p.stats_part || p.in_norm) {  // (one conv per launch: raft_conv2d_pair takes neither)
       if (bn == 64)
-        launch_halo_mt<KH, KW, 64, PREC, true>(l, grid, s);
+        launch_halo_mt<KH, KW, 64, PREC, true>(l, grid, s, q);
       else
-        launch_halo_mt<KH, KW, 32, PREC, true>(l, grid, s);
+        launch_halo_mt<KH, KW, 32, PREC, true>(l, grid, s, q);
       return;
     }
   }
   if (bn == 64)
-    launch_halo_mt<KH, KW, 64, PREC>(l, grid, s);
+    launch_halo_mt<KH, KW, 64, PREC>(l, grid, s, q);
   else
-    launch_halo_mt<KH, KW, 32, PREC>(l, grid, s);
+    launch_halo_mt<KH, KW, 32, PREC>(l, grid, s, q);
 }
 template <int KH, int KW>
-void launch_halo_k(const HaloLaunch& l, int bn, int th, dim3 grid, hipStream_t s) {
+void launch_halo_k(const HaloLaunch& l, int bn, int th, dim3 grid, hipStream_t s, ConvForm* q) {
   const int prec = l.a[0].p.precision;
   if (prec == RAFT_PREC_F16X3)
-    launch_halo_p<KH, KW, RAFT_PREC_F16X3>(l, bn, th, grid, s);
+    launch_halo_p<KH, KW, RAFT_PREC_F16X3>(l, bn, th, grid, s, q);
   else if (prec == RAFT_PREC_BF16)
-    launch_halo_p<KH, KW, RAFT_PREC_BF16>(l, bn, th, grid, s);
+    launch_halo_p<KH, KW, RAFT_PREC_BF16>(l, bn, th, grid, s, q);
   else
-    launch_halo_p<KH, KW, RAFT_PREC_F16>(l, bn, th, grid, s);
+    launch_halo_p<KH, KW, RAFT_PREC_F16>(l, bn, th, grid, s, q);
 }
 
 bool halo_enabled() {
@@ -1632,17 +1650,18 @@ double halo_mt_plan_cost(const HaloOperands& o, int th) {
   return cost;
 }
 
-void launch_halo(const HaloLaunch& l, int bn, int th, long wgs, hipStream_t s) {
+// (q != nullptr: the form query, halo_start)
+void launch_halo(const HaloLaunch& l, int bn, int th, long wgs, hipStream_t s, ConvForm* q) {
   const raft_conv2d_params& p = l.a[0].p;
   dim3 grid((unsigned)wgs);
   if (p.kh == 1 && p.kw == 1)
-    launch_halo_k<1, 1>(l, bn, th, grid, s);
+    launch_halo_k<1, 1>(l, bn, th, grid, s, q);
   else if (p.kh == 3)
-    launch_halo_k<3, 3>(l, bn, th, grid, s);
+    launch_halo_k<3, 3>(l, bn, th, grid, s, q);
   else if (p.kh == 1)
-    launch_halo_k<1, 5>(l, bn, th, grid, s);
+    launch_halo_k<1, 5>(l, bn, th, grid, s, q);
   else
-    launch_halo_k<5, 1>(l, bn, th, grid, s);
+    launch_halo_k<5, 1>(l, bn, th, grid, s, q);
 }
 
 
@@ -1770,19 +1789,21 @@ int conv_halo_tiles_per_wg(const HaloOperands& o) {
 
 // Launches the halo kernel when the conv is one it covers; returns 1 without launching
 // otherwise.  Arguments are already validated by raft_conv2d.
-int conv_halo_launch(const HaloOperands& o, hipStream_t s) {
+// q != nullptr (raft_conv2d_form): the same plan and dispatch, but *q is filled instead of the launch.
+int conv_halo_launch(const HaloOperands& o, hipStream_t s, ConvForm* q) {
   HaloLaunch l;
   int bn, th;
   long wgs;
   if (!halo_plan(o, l, bn, th, wgs)) return 1;
-  launch_halo(l, bn, th, wgs, s);
+  launch_halo(l, bn, th, wgs, s, q);
   return 0;
 }
 
 // Two independent convs of one shape class and precision in one launch (their tiles side
 // by side in the grid, one N-tile width for both); returns 1 without launching when the
 // pair does not qualify.
-int conv_halo_launch_pair(const HaloOperands& o0, const HaloOperands& o1, hipStream_t s) {
+// q != nullptr (raft_conv2d_pair_form): q[0] = q[1] = the shared launch's form, nothing launched.
+int conv_halo_launch_pair(const HaloOperands& o0, const HaloOperands& o1, hipStream_t s, ConvForm* q) {
   HaloLaunch l;
   if (!halo_enabled() || !halo_problem(o0, l.a[0]) || !halo_problem(o1, l.a[1])) return 1;
   const raft_conv2d_params &p0 = o0.p, &p1 = o1.p;
@@ -1801,7 +1822,8 @@ int conv_halo_launch_pair(const HaloOperands& o0, const HaloOperands& o1, hipStr
   l.a[1].gn = o1.n_pad / bn;
   const long t0 = s0 * l.a[0].gn, tiles = t0 + s1 * l.a[1].gn;
   if (tiles >= (1L << 31)) return 1;
-  launch_halo(l, bn, th, halo_plan_grid(l, bn, th, true), s);
+  launch_halo(l, bn, th, halo_plan_grid(l, bn, th, true), s, q);
+  if (q) q[1] = q[0];
   return 0;
 }
 

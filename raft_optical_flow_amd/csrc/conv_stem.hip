@@ -202,7 +202,7 @@ int conv_stem_stats_slots(const raft_conv2d_params& p, int k_pad) {
 // The stem kernel when the conv is one it covers (GATHER packing, 7x7 / stride 2 / pad 3, 3 input
 // channels, 64 outputs, a split-weight precision, an epilogue without a second input segment);
 // returns 1 without launching otherwise.  Arguments are validated by raft_conv2d.
-int conv_stem_launch(const raft_conv2d_params& p, int k_pad, hipStream_t s) {
+int conv_stem_launch(const raft_conv2d_params& p, int k_pad, hipStream_t s, ConvForm* form) {
   if (!stem_covers(p, k_pad)) return 1;
   StemArgs sa;
   sa.p = p;
@@ -210,6 +210,11 @@ int conv_stem_launch(const raft_conv2d_params& p, int k_pad, hipStream_t s) {
   sa.ty_n = cdiv(p.out_h, ST_TH);
   const long nt = (long)p.batch * sa.tx_n * sa.ty_n;
   if (nt >= (1L << 31)) return 1;
+  if (form) {  // raft_conv2d_form: the stem has one form
+    *form = ConvForm{};
+    form->kernel = RAFT_CONV_KERNEL_STEM;
+    return 0;
+  }
   sa.ntiles = (int)nt;
   // three work-groups per CU (LDS: 40 KB weight + 9.3 KB patch), each walking tiles
   const int grid = (int)(nt < 3 * 256 ? nt : 3 * 256);

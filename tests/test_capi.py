@@ -37,7 +37,7 @@ def test_library_exports_every_declared_symbol():
 
 def test_abi_queries_without_gpu():
     lib = _lib.load()
-    assert lib.raft_hip_abi_version() == _lib.ABI_VERSION == 18
+    assert lib.raft_hip_abi_version() == _lib.ABI_VERSION == 19
     # the library was built from the sources beside it (csrc/Makefile SRC_HASH)
     assert lib.raft_hip_source_hash().decode() == _lib.source_hash()
     assert lib.raft_hip_arch() == b"gfx950"
@@ -184,3 +184,112 @@ def test_corr_build_ws_bytes_prec_host_side():
         assert lib.raft_corr_build_ws_bytes_prec(1, 55, 128, 256, prec) == 0
     assert lib.raft_corr_build_ws_bytes_prec(1, 55, 128, 72, _lib.PREC_F16X3) == 0
     assert lib.raft_corr_build_ws_bytes_prec(1, 55, 128, 48, _lib.PREC_F16X3) == 0
+
+
+def test_conv_form_table_host_side():
+    """raft_conv2d_form (host logic only, the launch's own decision code): the shape -> form table of
+    conv_forms.py, which test_gpu_conv_epilogues.py runs every epilogue on.  256 CUs without a device.  The
+    existing two queries agree with it, and the 64-column f16x3 3x3 conv reports the K-split form (two
+    compute waves per SIMD), the product's default."""
+    import conv_forms as CF
+    lib = _lib.load()
+    prev = (lib.raft_conv2d_set_halo_ks(0), lib.raft_conv2d_set_halo_loaders(0))
+    assert prev == (2, 8)  # the defaults the table is written for
+    for c in CF.TABLE:
+        p = CF.host_params(c)
+        f = _lib.conv_form(p)
+        assert f.astuple() == c.form, (c.name, f.astuple(), c.form)
+        if f.kernel == CF.HALO:
+            assert lib.raft_conv2d_halo_tile_rows(ctypes.byref(p)) == f.tile_rows
+            assert lib.raft_conv2d_halo_tiles_per_wg(ctypes.byref(p)) == f.tiles_per_wg
+        else:
+            assert lib.raft_conv2d_halo_tile_rows(ctypes.byref(p)) == 0
+    assert CF.BY_NAME["h64-3x3-f16x3"].form[5] == 2 and CF.k_steps(CF.BY_NAME["h64-3x3-f16x3"]) == 27
+    assert CF.k_steps(CF.BY_NAME["h64-1x5-f16x3"]) == 15
+    # the knobs move the form: one compute wave per SIMD takes the 8-loader form, then the 4-loader one
+    p = CF.host_params(CF.BY_NAME["h64-3x3-f16x3"])
+    try:
+        lib.raft_conv2d_set_halo_ks(1)
+        assert _lib.conv_form(p).astuple() == (CF.HALO, 8, 64, 1, 8, 1, 0, 0)
+        lib.raft_conv2d_set_halo_loaders(4)
+        assert _lib.conv_form(p).astuple() == (CF.HALO, 8, 64, 1, 4, 1, 0, 0)
+    finally:
+        lib.raft_conv2d_set_halo_ks(prev[0])
+        lib.raft_conv2d_set_halo_loaders(prev[1])
+    # the stem takes LINEAR only at alpha 1: any other alpha runs the GEMM kernel's gather mode
+    stem = CF.BY_NAME["stem-f16x3"]
+    assert _lib.conv_form(CF.host_params(stem, _lib.EPI_RELU)).kernel == CF.STEM
+    assert _lib.conv_form(CF.host_params(stem, _lib.EPI_LINEAR, 0.25)).kernel == CF.GEMM
+    # an argument error is the launch's, and leaves the output alone
+    bad = CF.host_params(stem)
+    bad.n = 0
+    f = _lib.ConvForm(kernel=-5)
+    assert lib.raft_conv2d_form(ctypes.byref(bad), ctypes.byref(f)) == -1 and f.kernel == -5
+    assert lib.raft_conv2d_form(ctypes.byref(p), None) == -1
+
+
+def test_conv_pair_form_host_side():
+    """raft_conv2d_pair_form: a pair of one shape class shares a launch whose N-tile width follows the pair's
+    tile count, so a conv can take another form in the pair than alone (RAFT-full's convc2 | convf2 at 55x128:
+    convf2 runs 32-column tiles alone and the 64-column K-split form beside convc2); other pairs run in order,
+    each in its own form."""
+    import conv_forms as CF
+    lib = _lib.load()
+    assert lib.raft_conv2d_set_halo_ks(0) == 2
+
+    def conv(cin, n, k, B, H, W, prec="f16x3", base=1 << 20):
+        p = CF.host_params(CF.Conv("x", B, H, W, cin, n, k[0], k[1], 1, prec, None))
+        p.in0, p.out = base, base + (1 << 28)  # (stand-in operands 256 MiB apart: none meets another)
+        return p
+
+    far = 1 << 30
+    c2, f2 = conv(256, 192, (3, 3), 1, 55, 128), conv(128, 64, (3, 3), 1, 55, 128, base=far)
+    a, b, one = _lib.conv_pair_form(c2, f2)
+    assert one and a.astuple() == b.astuple() == (CF.HALO, 8, 64, 1, 4, 2, 0, 0)
+    assert _lib.conv_form(c2).astuple() == (CF.HALO, 8, 64, 1, 4, 2, 0, 0)
+    assert _lib.conv_form(f2).astuple() == (CF.HALO, 8, 32, 1, 8, 1, 0, 0)
+    # a 3x3 beside a 1x1: two launches, each conv's own form
+    x, y = conv(64, 64, (3, 3), 1, 8, 16), conv(64, 64, (1, 1), 1, 8, 16, base=far)
+    a, b, one = _lib.conv_pair_form(x, y)
+    assert not one and a.astuple() == _lib.conv_form(x).astuple() and b.astuple() == _lib.conv_form(y).astuple()
+    # both write the same rows: in order
+    y.out = x.out
+    assert _lib.conv_pair_form(x, y)[2] is False
+    out = (_lib.ConvForm * 2)()
+    assert lib.raft_conv2d_pair_form(None, None, out, ctypes.byref(ctypes.c_int())) == -1
+    assert b"null params" in lib.raft_hip_last_error()
+
+
+def test_conv_epilogue_preconditions_host_side():
+    """Every epilogue precondition of raft_conv2d is an argument error raised before any launch (the pointers
+    here are stand-ins that a launch would fault on), and the form query reports the same error."""
+    import conv_forms as CF
+    lib = _lib.load()
+    fake = 1 << 20
+    base = CF.BY_NAME["h32-3x3-f16x3"]  # N = 128
+
+    def rc(epilogue, **fields):
+        p = CF.host_params(base, epilogue)
+        for k, v in fields.items():
+            setattr(p, k, v)
+        r = lib.raft_conv2d(ctypes.byref(p), None)
+        msg = lib.raft_hip_last_error()
+        assert lib.raft_conv2d_form(ctypes.byref(p), ctypes.byref(_lib.ConvForm())) == r
+        return r, msg
+
+    r, msg = rc(_lib.EPI_RESID_RELU)
+    assert r == -1 and b"RESID_RELU needs aux0" in msg
+    for epi, name in ((_lib.EPI_GRU_ZR, b"GRU_ZR"), (_lib.EPI_TANH_RELU, b"TANH_RELU")):
+        ok = dict(aux0=fake, aux0_ld=128, out1=fake, out1_ld=128, split=64)
+        for broken in (dict(out1=None), dict(split=0), dict(split=128), dict(split=160), dict(split=48)):
+            r, msg = rc(epi, **{**ok, **broken})
+            assert r == -1 and name + b" needs" in msg, (name, broken, r, msg)
+    r, msg = rc(_lib.EPI_GRU_ZR, out1=fake, out1_ld=128, split=64)  # no aux0 (h)
+    assert r == -1 and b"GRU_ZR needs aux0" in msg
+    r, msg = rc(_lib.EPI_GRU_Q, aux0=fake, aux0_ld=128)
+    assert r == -1 and b"GRU_Q needs" in msg
+    r, msg = rc(_lib.EPI_GRU_Q, aux1=fake, aux1_ld=128)
+    assert r == -1 and b"GRU_Q needs" in msg
+    for unknown in (7, -1, 100):
+        r, msg = rc(unknown)
+        assert r == -1 and b"unknown epilogue" in msg
