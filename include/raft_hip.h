@@ -33,6 +33,8 @@
  *   raft_pad_replicate      <- InputPadder.pad (core/utils/utils.py:7-24, F.pad mode='replicate')
  *   raft_bilinear_sample    <- bilinear_sampler (core/utils/utils.py:57-71)
  *   raft_forward_interpolate <- forward_interpolate (core/utils/utils.py:26-54; scipy griddata 'nearest')
+ *   raft_ingest_frame       <- InputPadder.pad + RAFT.forward's normalisation, of one video frame
+ *                              (core/utils/utils.py:7-24, core/raft.py:164-169)
  */
 #ifndef RAFT_HIP_H_
 #define RAFT_HIP_H_
@@ -518,6 +520,30 @@ int raft_bilinear_sample(const float* img, const float* coords, float* out, floa
  * for the 1/8-resolution flow of the warm start: H*W <= RAFT_FI_MAX_POINTS (else RAFT_E_INVALID). */
 #define RAFT_FI_MAX_POINTS 65536
 int raft_forward_interpolate(const float* flow, float* out, int B, int H, int W, raft_stream_t stream);
+
+
+/* ---------------------------------------------------------------------------
+ * Video streams (StreamPlan / RAFT.stream): every frame is encoded once.
+ * Additive entries: they change no existing entry, so RAFT_HIP_ABI_VERSION stays 19.
+ * --------------------------------------------------------------------------- */
+/* InputPadder's rule (core/utils/utils.py:9-16): the replicate padding that makes H and W multiples
+ * of 8, centred (the reference's 'sintel' mode) or with every padding row at the bottom (any other
+ * mode); columns are centred in both.  Host arithmetic only; NULL outputs are skipped. */
+void raft_frame_pad(int H, int W, int centred, int* left, int* right, int* top, int* bottom);
+/* dtype tags of raft_ingest_frame's input */
+#define RAFT_FRAME_F32_NCHW 0 /* float32 [B][3][H][W], 0..255: what RAFT.forward takes */
+#define RAFT_FRAME_U8_NHWC 1  /* uint8 [B][H][W][3]: what a video decoder delivers */
+/* One frame of any size, in one launch: replicate-padded by raft_frame_pad's rule to Hp x Wp, written as
+ * (a) rows   NHWC rows [B*Hp*Wp][3] of 2 * (v / 255) - 1, the expression of raft_prep_images (bit-equal
+ *            to InputPadder.pad + raft_prep_images), and
+ * (b) padded the raw padded frame, float32 NCHW [B][3][Hp][Wp] (what the range guard's exact re-run reads).
+ * in, rows and padded are three distinct buffers. */
+int raft_ingest_frame(const void* in, int dtype, int B, int H, int W, int centred, float* rows, float* padded,
+                      raft_stream_t stream);
+/* A stream's current frame becomes its previous frame: three device copies (feature map, prepped
+ * rows, raw padded frame; element counts in floats) in one launch.  No pair may be in place. */
+int raft_stream_carry(const float* fmap_cur, float* fmap_prev, size_t n_fmap, const float* rows_cur, float* rows_prev,
+                      size_t n_rows, const float* raw_cur, float* raw_prev, size_t n_raw, raft_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -32,6 +32,9 @@ PRECISIONS = {"fp32": PREC_FP32, "f16x3": PREC_F16X3, "f16": PREC_F16, "bf16": P
 ABI_VERSION = 19
 RANGE_LIMIT = 32768.0  # RAFT_RANGE_LIMIT: |x| above it raises the f16x3 range guard
 
+FRAME_F32_NCHW = 0   # raft_ingest_frame input: float32 [B, 3, H, W]
+FRAME_U8_NHWC = 1    # uint8 [B, H, W, 3]
+
 EPI_LINEAR = 0
 EPI_RELU = 1
 EPI_RESID_RELU = 2
@@ -178,6 +181,9 @@ _PROTOS = {
     "raft_pad_replicate": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "raft_bilinear_sample": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "raft_forward_interpolate": (c_int, [P, P, c_int, c_int, c_int, P]),
+    "raft_frame_pad": (None, [c_int, c_int, c_int] + [ctypes.POINTER(c_int)] * 4),
+    "raft_ingest_frame": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, P]),
+    "raft_stream_carry": (c_int, [P, P, c_size_t, P, P, c_size_t, P, P, c_size_t, P]),
 }
 
 EXPORTED = tuple(_PROTOS)

@@ -8,6 +8,9 @@
 //   raft_forward_interpolate  forward_interpolate (core/utils/utils.py:26-54): the Sintel
 //                             warm start, scipy griddata(method='nearest') of the forward-
 //                             splatted flow, as an exact fp64 nearest-neighbour search
+//   raft_ingest_frame         the front end of a video stream: InputPadder.pad + the forward's
+//                             2 * (x / 255) - 1 of ONE frame (float NCHW or uint8 NHWC) in one launch
+//   raft_stream_carry         a stream's current frame becomes its previous one (three copies, one launch)
 #include "common.hpp"
 
 namespace raft {
@@ -125,6 +128,50 @@ __global__ __launch_bounds__(FI_T) void forward_interpolate_kernel(const float* 
   }
 }
 
+// One thread per padded pixel (b, y, x): the replicate-padded source pixel's three channels, read
+// from float NCHW or uint8 NHWC, go to the raw padded NCHW frame and, normalised with
+// prep_images_kernel's expression (misc.hip), to the NHWC rows the encoders read.
+template <bool U8>
+__global__ void ingest_frame_kernel(const void* __restrict__ in, float* __restrict__ rows,
+                                    float* __restrict__ padded, int B, int H, int W, int top, int left, int Hp,
+                                    int Wp) {
+  const long HWp = (long)Hp * Wp, HW = (long)H * W;
+  const long total = (long)B * HWp;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int b = (int)(i / HWp);
+    const long yx = i - (long)b * HWp;
+    const int y = (int)(yx / Wp), x = (int)(yx - (long)y * Wp);
+    const int sy = min(max(y - top, 0), H - 1), sx = min(max(x - left, 0), W - 1);
+    const long s = (long)sy * W + sx;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      float v;
+      if (U8)
+        v = (float)static_cast<const unsigned char*>(in)[((long)b * HW + s) * 3 + c];
+      else
+        v = static_cast<const float*>(in)[((long)b * 3 + c) * HW + s];
+      padded[((long)b * 3 + c) * HWp + yx] = v;
+      rows[i * 3 + c] = 2.0f * (v / 255.0f) - 1.0f;
+    }
+  }
+}
+
+// three device-to-device copies in one launch: segment k is n[k] elements of T from src[k] to dst[k]
+struct CarryArgs {
+  const void* src[3];
+  void* dst[3];
+  long n[3];
+};
+template <typename T>
+__global__ void stream_carry_kernel(CarryArgs a) {
+  const long n01 = a.n[0] + a.n[1], total = n01 + a.n[2];
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int k = i < a.n[0] ? 0 : i < n01 ? 1 : 2;
+    const long j = i - (k == 0 ? 0 : k == 1 ? a.n[0] : n01);
+    static_cast<T*>(a.dst[k])[j] = static_cast<const T*>(a.src[k])[j];
+  }
+}
+
 int grid_1d(long n) {
   long g = (n + 255) / 256;
   return (int)(g > 65536 ? 65536 : g < 1 ? 1 : g);
@@ -168,4 +215,60 @@ extern "C" int raft_forward_interpolate(const float* flow, float* out, int B, in
   dim3 grid((unsigned)cdiv_l((long)H * W, FI_T), (unsigned)B);
   hipLaunchKernelGGL(forward_interpolate_kernel, grid, dim3(FI_T), 0, as_stream(stream), flow, out, H, W);
   return check_launch("raft_forward_interpolate");
+}
+
+extern "C" void raft_frame_pad(int H, int W, int centred, int* left, int* right, int* top, int* bottom) {
+  // InputPadder.__init__ (core/utils/utils.py:9-16): -x mod 8, halves rounded down to the left / top
+  const int ph = H > 0 ? (8 - H % 8) % 8 : 0, pw = W > 0 ? (8 - W % 8) % 8 : 0;
+  const int t = centred ? ph / 2 : 0;
+  if (left) *left = pw / 2;
+  if (right) *right = pw - pw / 2;
+  if (top) *top = t;
+  if (bottom) *bottom = ph - t;
+}
+
+extern "C" int raft_ingest_frame(const void* in, int dtype, int B, int H, int W, int centred, float* rows,
+                                 float* padded, raft_stream_t stream) {
+  RAFT_REQUIRE(in && rows && padded, "raft_ingest_frame: null pointer");
+  RAFT_REQUIRE(B > 0 && H > 0 && W > 0, "raft_ingest_frame: bad size %d x %d x %d", B, H, W);
+  RAFT_REQUIRE(dtype == RAFT_FRAME_F32_NCHW || dtype == RAFT_FRAME_U8_NHWC, "raft_ingest_frame: unknown dtype tag %d",
+               dtype);
+  RAFT_REQUIRE(in != (const void*)rows && in != (const void*)padded && rows != padded,
+               "raft_ingest_frame: in-place is not supported");
+  int l, r, t, b;
+  raft_frame_pad(H, W, centred, &l, &r, &t, &b);
+  const int Hp = H + t + b, Wp = W + l + r;
+  const int grid = grid_1d((long)B * Hp * Wp);
+  if (dtype == RAFT_FRAME_U8_NHWC)
+    hipLaunchKernelGGL(ingest_frame_kernel<true>, dim3(grid), dim3(256), 0, as_stream(stream), in, rows, padded, B, H,
+                       W, t, l, Hp, Wp);
+  else
+    hipLaunchKernelGGL(ingest_frame_kernel<false>, dim3(grid), dim3(256), 0, as_stream(stream), in, rows, padded, B,
+                       H, W, t, l, Hp, Wp);
+  return check_launch("raft_ingest_frame");
+}
+
+extern "C" int raft_stream_carry(const float* fmap_cur, float* fmap_prev, size_t n_fmap, const float* rows_cur,
+                                 float* rows_prev, size_t n_rows, const float* raw_cur, float* raw_prev, size_t n_raw,
+                                 raft_stream_t stream) {
+  RAFT_REQUIRE(fmap_cur && fmap_prev && rows_cur && rows_prev && raw_cur && raw_prev,
+               "raft_stream_carry: null pointer");
+  RAFT_REQUIRE(n_fmap > 0 && n_rows > 0 && n_raw > 0 && n_fmap < (1UL << 40) && n_rows < (1UL << 40) &&
+                   n_raw < (1UL << 40),
+               "raft_stream_carry: bad size");
+  RAFT_REQUIRE(fmap_cur != fmap_prev && rows_cur != rows_prev && raw_cur != raw_prev,
+               "raft_stream_carry: in-place is not supported");
+  CarryArgs a{{fmap_cur, rows_cur, raw_cur}, {fmap_prev, rows_prev, raw_prev}, {(long)n_fmap, (long)n_rows, (long)n_raw}};
+  bool vec = true;
+  for (int k = 0; k < 3; ++k)
+    vec = vec && a.n[k] % 4 == 0 && (((uintptr_t)a.src[k] | (uintptr_t)a.dst[k]) & 15) == 0;
+  if (vec) {
+    for (int k = 0; k < 3; ++k) a.n[k] /= 4;
+    hipLaunchKernelGGL(stream_carry_kernel<float4>, dim3(grid_1d(a.n[0] + a.n[1] + a.n[2])), dim3(256), 0,
+                       as_stream(stream), a);
+  } else {
+    hipLaunchKernelGGL(stream_carry_kernel<float>, dim3(grid_1d(a.n[0] + a.n[1] + a.n[2])), dim3(256), 0,
+                       as_stream(stream), a);
+  }
+  return check_launch("raft_stream_carry");
 }

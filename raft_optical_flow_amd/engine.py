@@ -6,7 +6,8 @@ pyramid, recurrent state) and records the exact sequence of C-ABI kernel
 launches with their fixed pointers.  `RaftPlan.run()` replays the launch list
 on the current stream; `RaftPlan.capture()` records it into a hipGraph
 (torch.cuda.CUDAGraph on ROCm) so the 32-iteration refinement loop replays
-with no host work per kernel.
+with no host work per kernel.  `StreamPlan` (at the end of the module) is the
+same for a video: one frame per step, every frame encoded once (RAFT.stream).
 
 Buffer layout of the recurrent state (P = B * H/8 * W/8 rows), RAFT-full:
   HX   [P, 384]  = h (128) | motion conv (126) | flow (2) | inp (128)
@@ -624,6 +625,116 @@ def _order_context_branch(L, f0, c0):
     L[f0:] = merged
 
 
+def plan_correlation(plan, L, A: Arena, pk: PackedRaft, B, h, w, fmap1, fmap2, alternate):
+    """The correlation volume of a pair (all-pairs: the pyramid build, plan.pyramid) or, for the alternate
+    path, fmap2's pooled levels (plan.f2levels), from the two feature maps' rows."""
+    C, lv = pk.fdim, pk.levels
+    div = K.sqrt_c(C)
+    if not alternate:
+        plan.pyramid = A.flat(K.pyramid_floats(B, h, w, lv))
+        # the correlation GEMM follows the conv arithmetic: exact f32 MFMA in "fp32"
+        # mode, the fp32-accurate f16 split otherwise (raft_hip.h)
+        cprec = _lib.PREC_FP32 if pk.precision == _lib.PREC_FP32 else _lib.PREC_F16X3
+        # (f16x3: fmaps split once into the workspace, the volume on 256 x 256 tiles: raft_hip.h)
+        # (the workspace only where the library takes that path: raft_corr_build_ws)
+        # (the library's own rule: raft_corr_build_ws_bytes_prec is 0 where that kernel does not apply)
+        wsb = int(_lib.load().raft_corr_build_ws_bytes_prec(B, h, w, C, cprec))
+        fits4 = wsb > 0
+        plan.corr_ws = A.flat((wsb + 3) // 4) if fits4 else None
+        L.append(Launch("raft_corr_build_ws", fmap1.data_ptr(), fmap2.data_ptr(), C, B, h, w, C, lv, div,
+                        cprec, plan.pyramid.data_ptr(), plan.corr_ws.data_ptr() if fits4 else None, wsb))
+    else:
+        # AlternateCorrBlock pools num_levels times (core/corr.py:157-161); the
+        # last level is never used, but its existence is the reference's size check.
+        hh, ww = h, w
+        for _ in range(lv):
+            hh, ww = hh // 2, ww // 2
+            if hh < 1 or ww < 1:
+                raise RuntimeError(f"AlternateCorrBlock: feature map {h}x{w} too small for {lv} pooling levels")
+        plan.f2levels = [(fmap2, h, w)]
+        hh, ww = h, w
+        for _ in range(lv - 1):
+            nh, nw = hh // 2, ww // 2
+            dst = A.rows(B * nh * nw, C)
+            L.append(Launch("raft_avgpool2_nhwc", plan.f2levels[-1][0].data_ptr(), dst.data_ptr(), B, hh, ww, C))
+            plan.f2levels.append((dst, nh, nw))
+            hh, ww = nh, nw
+
+
+def plan_refinement(plan, L, pk: PackedRaft, ub: UpdateBuffers, B, H, W, iters, test_mode, alternate, fmap1, device):
+    """From the initial coordinates to flow_low: raft_init_coords (+ plan.flow_init), the `iters` lookups and
+    update steps, the upsampling (core/raft.py:208-246) and raft_flow_from_coords.  Reads plan.pyramid /
+    plan.f2levels (plan_correlation) and plan.flow_init; sets plan.loop_start / loop_end / flow_up and
+    plan.flow_low (kept where the plan allocated it already)."""
+    pu = pk.update
+    h, w = H // 8, W // 8
+    r, lv = pk.radius, pk.levels
+    corr_ld = lv * (2 * r + 1) ** 2
+    C = pk.fdim
+    div = K.sqrt_c(C)
+    L.append(Launch("raft_init_coords", ub.coords.data_ptr(),
+                    plan.flow_init.data_ptr() if plan.flow_init is not None else None, B, h, w))
+    plan.loop_start = len(L)
+    plan.flow_up = [torch.empty(B, 2, H, W, device=device) for _ in range(1 if test_mode else iters)]
+    flow_slot = ub.flow_off(pu)
+    gflag = plan.range_flag.data_ptr() if plan.guarded else None
+    # all-pairs RAFT-full: the motion encoder's convf1 runs inside the lookup launch
+    # (its own launch would be a K = 98 GEMM behind a launch's fixed cost)
+    # (alternate corr: convf1 as its own VALU launch, raft_convf1_flow: the alternate lookup's
+    # launch has no room for it)
+    fuse_f1 = convf1_fused(pu) and os.environ.get("RAFT_CONV_PAIR", "1") != "0"
+    if fuse_f1:
+        f1w = convf1_vec_weight(pu)
+        f1b = pu.convf1.bias.data_ptr() if pu.convf1.bias is not None else None
+    fuse_c1 = fuse_f1 and not alternate and convc1_fused(pk)
+    if fuse_c1:
+        c1w, f1w_frag = frag_weight(pu.convc1), frag_weight(pu.convf1)
+        c1b = pu.convc1.bias.data_ptr() if pu.convc1.bias is not None else None
+    for it in range(iters):
+        last = it == iters - 1
+        if fuse_c1:
+            L.append(Launch("raft_corr_lookup_conv", plan.pyramid.data_ptr(), B, h, w, lv, r, ub.coords.data_ptr(),
+                            ub.hx.data_ptr() + 4 * flow_slot, pu.ld, gflag, pu.convc1.precision, c1w.data_ptr(),
+                            c1b, pu.convc1.n, ub.cor1.data_ptr(), ub.cor1.shape[1], gflag, f1w_frag.data_ptr(), f1b,
+                            pu.convf1.n, pu.convf1.kh, ub.flo1.data_ptr(), ub.flo1.shape[1], gflag,
+                            keep=(f1w_frag, c1w)))
+        elif fuse_f1 and not alternate:
+            L.append(Launch("raft_corr_lookup_convf1", plan.pyramid.data_ptr(), B, h, w, lv, r,
+                            ub.coords.data_ptr(), 0, ub.corr.data_ptr(), corr_ld, 0,
+                            ub.hx.data_ptr() + 4 * flow_slot, pu.ld, gflag, f1w.data_ptr(), f1b, pu.convf1.n,
+                            pu.convf1.kh, pu.convf1.precision, ub.flo1.data_ptr(), ub.flo1.shape[1], gflag,
+                            keep=f1w))
+        elif not alternate:
+            L.append(Launch("raft_corr_lookup", plan.pyramid.data_ptr(), B, h, w, lv, r, ub.coords.data_ptr(), 0,
+                            ub.corr.data_ptr(), corr_ld, 0, ub.hx.data_ptr() + 4 * flow_slot, pu.ld, gflag))
+        else:
+            # every level in one call (one launch for RAFT's r = 4, C = 256: raft_hip.h)
+            arrs = K.alt_levels_args(plan.f2levels)
+            # exact fp32 products in "fp32" mode (the range guard's re-run), the f16x3 box GEMM otherwise
+            aprec = _lib.PREC_FP32 if pk.precision == _lib.PREC_FP32 else _lib.PREC_F16X3
+            L.append(Launch("raft_alt_corr_lookup_levels_prec", fmap1.data_ptr(), *arrs, len(plan.f2levels),
+                            ub.coords.data_ptr(), 0, ub.corr.data_ptr(), corr_ld, B, h, w, C, r, div,
+                            ub.hx.data_ptr() + 4 * flow_slot, pu.ld, gflag, aprec, keep=arrs))
+            if fuse_f1:
+                L.append(Launch("raft_convf1_flow", ub.coords.data_ptr(), 0, B, h, w, f1w.data_ptr(), f1b,
+                                pu.convf1.n, pu.convf1.kh, pu.convf1.precision, ub.flo1.data_ptr(),
+                                ub.flo1.shape[1], gflag, keep=f1w))
+        want_up = last or not test_mode
+        plan_update(L, pu, ub, B, h, w, with_mask=want_up and not pu.small, convf1_done=fuse_f1,
+                    convc1_done=fuse_c1, last=last)
+        if want_up:
+            dst = plan.flow_up[-1 if test_mode else it]
+            if pu.small:
+                L.append(Launch("raft_upflow8", ub.coords.data_ptr(), dst.data_ptr(), B, h, w))
+            else:
+                L.append(Launch("raft_convex_upsample", ub.coords.data_ptr(), ub.mask.data_ptr(), 576,
+                                dst.data_ptr(), B, h, w))
+    plan.loop_end = len(L)
+    if getattr(plan, "flow_low", None) is None:
+        plan.flow_low = torch.empty(B, 2, h, w, device=device)
+    L.append(Launch("raft_flow_from_coords", ub.coords.data_ptr(), plan.flow_low.data_ptr(), B, h, w))
+
+
 # ----------------------------------------------------------------------------
 # The whole forward
 # ----------------------------------------------------------------------------
@@ -675,43 +786,11 @@ class RaftPlan:
         fm = Rows(A.rows(2 * B * h * w, pk.fdim))
         _conv(L, pk.fnet.head, x, 2 * B, h, w, fm)
         self.fmap = fm.t
-        r, lv = pk.radius, pk.levels
-        corr_ld = lv * (2 * r + 1) ** 2
         pu = pk.update
-        ub = self.ub = UpdateBuffers(A, pu, P, corr_ld)
+        ub = self.ub = UpdateBuffers(A, pu, P, pk.levels * (2 * pk.radius + 1) ** 2)
         fmap1 = fm.t[: B * h * w]
         fmap2 = fm.t[B * h * w:]
-        C = pk.fdim
-        div = K.sqrt_c(C)
-        if not alternate:
-            self.pyramid = A.flat(K.pyramid_floats(B, h, w, lv))
-            # the correlation GEMM follows the conv arithmetic: exact f32 MFMA in "fp32"
-            # mode, the fp32-accurate f16 split otherwise (raft_hip.h)
-            cprec = _lib.PREC_FP32 if pk.precision == _lib.PREC_FP32 else _lib.PREC_F16X3
-            # (f16x3: fmaps split once into the workspace, the volume on 256 x 256 tiles: raft_hip.h)
-            # (the workspace only where the library takes that path: raft_corr_build_ws)
-            # (the library's own rule: raft_corr_build_ws_bytes_prec is 0 where that kernel does not apply)
-            wsb = int(_lib.load().raft_corr_build_ws_bytes_prec(B, h, w, C, cprec))
-            fits4 = wsb > 0
-            self.corr_ws = A.flat((wsb + 3) // 4) if fits4 else None
-            L.append(Launch("raft_corr_build_ws", fmap1.data_ptr(), fmap2.data_ptr(), C, B, h, w, C, lv, div,
-                            cprec, self.pyramid.data_ptr(), self.corr_ws.data_ptr() if fits4 else None, wsb))
-        else:
-            # AlternateCorrBlock pools num_levels times (core/corr.py:157-161); the
-            # last level is never used, but its existence is the reference's size check.
-            hh, ww = h, w
-            for _ in range(lv):
-                hh, ww = hh // 2, ww // 2
-                if hh < 1 or ww < 1:
-                    raise RuntimeError(f"AlternateCorrBlock: feature map {h}x{w} too small for {lv} pooling levels")
-            self.f2levels = [(fmap2, h, w)]
-            hh, ww = h, w
-            for _ in range(lv - 1):
-                nh, nw = hh // 2, ww // 2
-                dst = A.rows(B * nh * nw, C)
-                L.append(Launch("raft_avgpool2_nhwc", self.f2levels[-1][0].data_ptr(), dst.data_ptr(), B, hh, ww, C))
-                self.f2levels.append((dst, nh, nw))
-                hh, ww = nh, nw
+        plan_correlation(self, L, A, pk, B, h, w, fmap1, fmap2, alternate)
         # context network (core/raft.py:193-200): tanh/relu split fused into its last conv
         n_ctx = len(L)
         xc, _, _ = plan_encoder_trunk(L, A, pk.cnet, Rows(prep.t[: B * H * W]), B, H, W)
@@ -723,66 +802,7 @@ class RaftPlan:
                     l.side = True
             _order_context_branch(L, L.index(K.FORK) + 1, n_ctx)
             L.append(K.JOIN)
-        L.append(Launch("raft_init_coords", ub.coords.data_ptr(),
-                        self.flow_init.data_ptr() if self.flow_init is not None else None, B, h, w))
-        self.loop_start = len(L)
-        self.flow_up = [torch.empty(B, 2, H, W, device=device) for _ in range(1 if test_mode else iters)]
-        flow_slot = ub.flow_off(pu)
-        gflag = self.range_flag.data_ptr() if self.guarded else None
-        # all-pairs RAFT-full: the motion encoder's convf1 runs inside the lookup launch
-        # (its own launch would be a K = 98 GEMM behind a launch's fixed cost)
-        # (alternate corr: convf1 as its own VALU launch, raft_convf1_flow: the alternate lookup's
-        # launch has no room for it)
-        fuse_f1 = convf1_fused(pu) and os.environ.get("RAFT_CONV_PAIR", "1") != "0"
-        if fuse_f1:
-            f1w = convf1_vec_weight(pu)
-            f1b = pu.convf1.bias.data_ptr() if pu.convf1.bias is not None else None
-        fuse_c1 = fuse_f1 and not alternate and convc1_fused(pk)
-        if fuse_c1:
-            c1w, f1w_frag = frag_weight(pu.convc1), frag_weight(pu.convf1)
-            c1b = pu.convc1.bias.data_ptr() if pu.convc1.bias is not None else None
-        for it in range(iters):
-            last = it == iters - 1
-            if fuse_c1:
-                L.append(Launch("raft_corr_lookup_conv", self.pyramid.data_ptr(), B, h, w, lv, r, ub.coords.data_ptr(),
-                                ub.hx.data_ptr() + 4 * flow_slot, pu.ld, gflag, pu.convc1.precision, c1w.data_ptr(),
-                                c1b, pu.convc1.n, ub.cor1.data_ptr(), ub.cor1.shape[1], gflag, f1w_frag.data_ptr(), f1b,
-                                pu.convf1.n, pu.convf1.kh, ub.flo1.data_ptr(), ub.flo1.shape[1], gflag,
-                                keep=(f1w_frag, c1w)))
-            elif fuse_f1 and not alternate:
-                L.append(Launch("raft_corr_lookup_convf1", self.pyramid.data_ptr(), B, h, w, lv, r,
-                                ub.coords.data_ptr(), 0, ub.corr.data_ptr(), corr_ld, 0,
-                                ub.hx.data_ptr() + 4 * flow_slot, pu.ld, gflag, f1w.data_ptr(), f1b, pu.convf1.n,
-                                pu.convf1.kh, pu.convf1.precision, ub.flo1.data_ptr(), ub.flo1.shape[1], gflag,
-                                keep=f1w))
-            elif not alternate:
-                L.append(Launch("raft_corr_lookup", self.pyramid.data_ptr(), B, h, w, lv, r, ub.coords.data_ptr(), 0,
-                                ub.corr.data_ptr(), corr_ld, 0, ub.hx.data_ptr() + 4 * flow_slot, pu.ld, gflag))
-            else:
-                # every level in one call (one launch for RAFT's r = 4, C = 256: raft_hip.h)
-                arrs = K.alt_levels_args(self.f2levels)
-                # exact fp32 products in "fp32" mode (the range guard's re-run), the f16x3 box GEMM otherwise
-                aprec = _lib.PREC_FP32 if pk.precision == _lib.PREC_FP32 else _lib.PREC_F16X3
-                L.append(Launch("raft_alt_corr_lookup_levels_prec", fmap1.data_ptr(), *arrs, len(self.f2levels),
-                                ub.coords.data_ptr(), 0, ub.corr.data_ptr(), corr_ld, B, h, w, C, r, div,
-                                ub.hx.data_ptr() + 4 * flow_slot, pu.ld, gflag, aprec, keep=arrs))
-                if fuse_f1:
-                    L.append(Launch("raft_convf1_flow", ub.coords.data_ptr(), 0, B, h, w, f1w.data_ptr(), f1b,
-                                    pu.convf1.n, pu.convf1.kh, pu.convf1.precision, ub.flo1.data_ptr(),
-                                    ub.flo1.shape[1], gflag, keep=f1w))
-            want_up = last or not test_mode
-            plan_update(L, pu, ub, B, h, w, with_mask=want_up and not pu.small, convf1_done=fuse_f1,
-                        convc1_done=fuse_c1, last=last)
-            if want_up:
-                dst = self.flow_up[-1 if test_mode else it]
-                if pu.small:
-                    L.append(Launch("raft_upflow8", ub.coords.data_ptr(), dst.data_ptr(), B, h, w))
-                else:
-                    L.append(Launch("raft_convex_upsample", ub.coords.data_ptr(), ub.mask.data_ptr(), 576,
-                                    dst.data_ptr(), B, h, w))
-        self.loop_end = len(L)
-        self.flow_low = torch.empty(B, 2, h, w, device=device)
-        L.append(Launch("raft_flow_from_coords", ub.coords.data_ptr(), self.flow_low.data_ptr(), B, h, w))
+        plan_refinement(self, L, pk, ub, B, H, W, iters, test_mode, alternate, fmap1, device)
 
     # -- execution --------------------------------------------------------
     def run(self):
@@ -832,6 +852,176 @@ class RaftPlan:
         if self.test_mode:
             return f(self.flow_low), f(self.flow_up[0])
         return [f(t) for t in self.flow_up]
+
+    def kernel_names(self):
+        return [l.name for l in self.launches if isinstance(l, Launch)]
+
+
+# ----------------------------------------------------------------------------
+# Video: one frame per step
+# ----------------------------------------------------------------------------
+
+
+def frame_pad(H, W, centred):
+    """[left, right, top, bottom] of raft_frame_pad: InputPadder's `_pad` (core/utils/utils.py:9-16)."""
+    out = [ctypes.c_int() for _ in range(4)]
+    _lib.load().raft_frame_pad(int(H), int(W), int(bool(centred)), *[ctypes.byref(v) for v in out])
+    return [v.value for v in out]
+
+
+def frame_layout(frame: torch.Tensor):
+    """(dtype tag of raft_ingest_frame, B, H, W) of a frame: float32 NCHW [B,3,H,W] or uint8 NHWC [B,H,W,3]."""
+    if frame.dim() == 4 and frame.dtype == torch.float32 and frame.shape[1] == 3:
+        return _lib.FRAME_F32_NCHW, frame.shape[0], frame.shape[2], frame.shape[3]
+    if frame.dim() == 4 and frame.dtype == torch.uint8 and frame.shape[3] == 3:
+        return _lib.FRAME_U8_NHWC, frame.shape[0], frame.shape[1], frame.shape[2]
+    raise ValueError("a frame is float32 [B, 3, H, W] (0..255) or uint8 [B, H, W, 3], got "
+                     f"{frame.dtype} {tuple(frame.shape)}")
+
+
+class StreamPlan:
+    """RAFT over consecutive frames as a fixed launch list per step: every frame passes through the
+    feature network once.  The plan holds two slots (feature map, prepped rows, raw padded frame):
+    `prev` = image1 and `cur` = image2 of the pair a step computes.  One step:
+
+      raft_stream_carry   cur -> prev (the frame of the step before becomes image1)
+      raft_ingest_frame   the staged frame -> cur rows + cur raw frame
+      FORK
+        main: fnet trunk + head on cur only (n_img = B), then the correlation build (or the
+              alternate path's fmap2 pooling) with fmap1 = prev, fmap2 = cur
+        side: cnet + the GRU context terms on prev's rows; warm start: raft_forward_interpolate
+              (flow_low of the step before -> flow_init)
+      JOIN
+      raft_init_coords ... raft_flow_from_coords, plan_refinement as RaftPlan's
+
+    The carry opens the step instead of closing it, so that after a step BOTH raw frames of its pair
+    are still in the plan: the range guard's exact re-run and a rebuild after a weight change read
+    them.  `prime()` (the first frame after a reset) is the short list ingest + fnet."""
+
+    def __init__(self, pk: PackedRaft, B, H, W, iters, dtype_tag=_lib.FRAME_F32_NCHW, centred=True, alternate=False,
+                 warm_start=False, device=None, range_guard=True):
+        self.pk, self.B, self.H, self.W, self.iters = pk, B, H, W, iters
+        self.dtype_tag, self.centred, self.alternate, self.warm_start = dtype_tag, bool(centred), alternate, warm_start
+        self.test_mode = True
+        self.device = device
+        self.pad = frame_pad(H, W, centred)
+        self.Hp, self.Wp = H + self.pad[2] + self.pad[3], W + self.pad[0] + self.pad[1]
+        self.guarded = range_guard and pk.precision == _lib.PREC_F16X3
+        self.range_flag = torch.zeros(1, dtype=torch.int32, device=device)
+        _GUARD["flag"] = self.range_flag if self.guarded else None
+        try:
+            self._build(pk, B, iters, alternate, device)
+        finally:
+            _GUARD["flag"] = None
+        self.graph = None
+        self.side_stream = None
+        self.runs = 0
+
+    def _build(self, pk, B, iters, alternate, device):
+        A = self.arena = Arena(device)
+        H, W, Hp, Wp = self.H, self.W, self.Hp, self.Wp
+        h, w = Hp // 8, Wp // 8
+        self.h, self.w = h, w
+        P = B * h * w
+        if self.dtype_tag == _lib.FRAME_U8_NHWC:
+            self.frame_in = torch.empty(B, H, W, 3, dtype=torch.uint8, device=device)
+        else:
+            self.frame_in = torch.empty(B, 3, H, W, device=device)
+        self.rows_prev, self.rows_cur = A.rows(B * Hp * Wp, 3), A.rows(B * Hp * Wp, 3)
+        self.raw_prev, self.raw_cur = (torch.empty(B, 3, Hp, Wp, device=device) for _ in range(2))
+        self.fmap_prev, self.fmap_cur = A.rows(P, pk.fdim), A.rows(P, pk.fdim)
+        self.flow_init = torch.zeros(B, 2, h, w, device=device) if self.warm_start else None
+        self.flow_low = torch.zeros(B, 2, h, w, device=device)
+        carry = Launch("raft_stream_carry", self.fmap_cur.data_ptr(), self.fmap_prev.data_ptr(), self.fmap_cur.numel(),
+                       self.rows_cur.data_ptr(), self.rows_prev.data_ptr(), self.rows_cur.numel(),
+                       self.raw_cur.data_ptr(), self.raw_prev.data_ptr(), self.raw_cur.numel())
+        self._ingest = Launch("raft_ingest_frame", self.frame_in.data_ptr(), self.dtype_tag, B, H, W, int(self.centred),
+                              self.rows_cur.data_ptr(), self.raw_cur.data_ptr())
+        # feature network on the current frame alone (core/raft.py:177-182 encodes [img1; img2])
+        F = self._fnet = []
+        x, fh_, fw_ = plan_encoder_trunk(F, A, pk.fnet, Rows(self.rows_cur), B, Hp, Wp)
+        assert (fh_, fw_) == (h, w), ((fh_, fw_), (h, w))
+        _conv(F, pk.fnet.head, x, B, h, w, Rows(self.fmap_cur))
+        self.prime_launches = [self._ingest] + F
+        L = self.launches = [carry, self._ingest, K.FORK] + F
+        pu = pk.update
+        ub = self.ub = UpdateBuffers(A, pu, P, pk.levels * (2 * pk.radius + 1) ** 2)
+        plan_correlation(self, L, A, pk, B, h, w, self.fmap_prev, self.fmap_cur, alternate)
+        # context network of the previous frame (image1, core/raft.py:193-200), beside the feature network
+        n_ctx = len(L)
+        xc, _, _ = plan_encoder_trunk(L, A, pk.cnet, Rows(self.rows_prev), B, Hp, Wp)
+        _conv(L, pk.cnet.head, xc, B, h, w, ub.h(pu), epilogue=_lib.EPI_TANH_RELU, split=pk.hdim, out1=ub.inp(pu))
+        plan_gru_context(L, pu, ub, B, h, w)
+        if self.warm_start:
+            # evaluate.py:37-41's warm start on the device: it reads only the flow_low of the step before
+            L.append(Launch("raft_forward_interpolate", self.flow_low.data_ptr(), self.flow_init.data_ptr(), B, h, w))
+        for l in L[n_ctx:]:
+            l.side = True
+        L.append(K.JOIN)
+        plan_refinement(self, L, pk, ub, B, Hp, Wp, iters, True, alternate, self.fmap_prev, device)
+
+    # -- state --------------------------------------------------------------
+    def reset(self):
+        """Sequence boundary: the next frame primes the stream; a warm start begins from zero flow."""
+        self.flow_low.zero_()
+
+    def _state(self):
+        """What a step reads from the step before it (after the carry: the `cur` slot and flow_low)."""
+        return [self.fmap_cur, self.rows_cur, self.raw_cur, self.flow_low]
+
+    # -- execution ------------------------------------------------------------
+    def _side(self):
+        if self.side_stream is None:
+            self.side_stream = torch.cuda.Stream(device=self.device)
+        return self.side_stream
+
+    def prime(self, raw=None):
+        """Encode the first frame of a sequence into the `cur` slot: the staged frame, or (a plan rebuilt
+        mid-stream) a raw padded frame [B,3,Hp,Wp] another plan held."""
+        if raw is None:
+            K.run(self.prime_launches)
+            return
+        _lib.call("raft_ingest_frame", raw.data_ptr(), _lib.FRAME_F32_NCHW, self.B, self.Hp, self.Wp, 1,
+                  self.rows_cur.data_ptr(), self.raw_cur.data_ptr(), K.stream_handle())
+        K.run(self._fnet)
+
+    def run(self):
+        K.run(self.launches, self._side())
+        self.runs += 1
+
+    def capture(self):
+        """Record a step into a hipGraph, as RaftPlan.capture: a warm-up run, then the capture.  The
+        warm-up is a whole step, so the state it advanced is put back before the real one."""
+        torch.cuda.synchronize()
+        keep = [t.clone() for t in self._state()]
+        self.run()  # warm-up outside capture (first-launch code object loads)
+        for t, k in zip(self._state(), keep):
+            t.copy_(k)
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            self.run()
+        torch.cuda.synchronize()
+        self.graph = g
+        return g
+
+    def replay(self):
+        if self.graph is None:
+            self.capture()
+        self.graph.replay()
+
+    def release(self):
+        """Drop the graph and every device buffer of the plan (it cannot run afterwards)."""
+        if self.graph is not None:
+            torch.cuda.synchronize(self.device)
+            self.graph.reset()
+            self.graph = None
+        self.launches, self.prime_launches, self._fnet, self._ingest = [], [], [], None
+        self.arena.bufs.clear()
+        for name in ("pyramid", "corr_ws", "f2levels", "ub", "frame_in", "rows_prev", "rows_cur", "raw_prev", "raw_cur",
+                     "fmap_prev", "fmap_cur", "flow_init", "flow_low", "flow_up", "range_flag"):
+            if hasattr(self, name):
+                setattr(self, name, None)
 
     def kernel_names(self):
         return [l.name for l in self.launches if isinstance(l, Launch)]

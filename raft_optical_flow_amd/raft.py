@@ -20,6 +20,9 @@ eager launches).  Plans live in a small LRU (RAFT_MAX_PLANS, default 2): a
 plan pins its correlation pyramid (275 MB at 440x1024) and buffers, so
 evaluate.py's many KITTI sizes do not accumulate device memory.
 
+Video: `model.stream(iters, warm_start, pad_mode)` returns a FlowStream (below): `push(frame)`
+gives the flow of (previous frame, this frame) and encodes every frame once (engine.StreamPlan).
+
 f16x3 range guard: the default fp32-accurate split arithmetic holds only while every
 conv input stays below 65504 in magnitude (include/raft_hip.h).  The convs and lookups
 whose outputs feed split convs raise a device flag above 2^15.  `model.range_guard`
@@ -52,7 +55,7 @@ import torch
 import torch.nn as nn
 
 from . import kernels as K
-from .engine import PackedRaft, RaftPlan
+from .engine import PackedRaft, RaftPlan, StreamPlan, frame_layout, frame_pad
 from .extractor import BasicEncoder, SmallEncoder
 from .update import BasicUpdateBlock, SmallUpdateBlock
 from .utils.utils import coords_grid
@@ -288,8 +291,7 @@ class RAFT(nn.Module):
             with torch.cuda.device(image1.device):
                 return self.forward(image1, image2, iters, flow_init, upsample, test_mode, _prec)
         if self.training:
-            raise NotImplementedError("raft_optical_flow_amd.RAFT is an inference path: call model.eval() "
-                                      "(training / BatchNorm batch statistics are out of scope)")
+            raise NotImplementedError(_TRAINING_MSG)
         K.require_device(image1, image2, flow_init)
         if image1.shape != image2.shape or image1.dim() != 4 or image1.shape[1] != 3:
             raise ValueError(f"images must both be [N, 3, H, W], got {tuple(image1.shape)} / {tuple(image2.shape)}")
@@ -352,6 +354,189 @@ class RAFT(nn.Module):
         if len(self._pending) > self._MAX_PENDING:
             self.check_range_guard(block=False)
         return outs
+
+
+    def stream(self, iters=12, warm_start=False, pad_mode="sintel"):
+        """A FlowStream over consecutive video frames: `push(frame)` returns (flow_low, flow_up) of
+        (previous frame, this frame), and every frame passes through the feature network once."""
+        return FlowStream(self, iters, warm_start, pad_mode)
+
+
+_TRAINING_MSG = ("raft_optical_flow_amd.RAFT is an inference path: call model.eval() "
+                 "(training / BatchNorm batch statistics are out of scope)")
+
+
+class FlowStream:
+    """Optical flow over a video, one frame per call (RAFT.stream).
+
+      s = model.stream(iters=12, warm_start=False, pad_mode="sintel")
+      out = s.push(frame)   # None for the first frame after reset(); then (flow_low, flow_up) of
+                            # (previous frame, this frame)
+      s.reset()             # sequence boundary
+      s.close()             # releases graph and buffers (also at garbage collection / `with` exit)
+      s.last_flow_init      # [B,2,h,w] the last step started from (None when warm_start=False)
+
+    A frame is float32 [B,3,H,W] in 0..255 or uint8 [B,H,W,3], of any size (it is replicate-padded as
+    InputPadder(pad_mode) does; flow_up comes back at the frame's own size, flow_low at 1/8 of the
+    padded one); B > 1 is B independent streams in lockstep.  The first push fixes shape and dtype.
+    What push returns equals model(pad(prev), pad(cur), iters, flow_init=s.last_flow_init,
+    test_mode=True) + unpad.  With warm_start every pair starts from forward_interpolate of the
+    pair before (evaluate.py:37-41), computed on the device inside the step.
+
+    The stream owns its engine.StreamPlan: it is not in the model's plan cache (max_plans,
+    release_plans() do not see it).  The range guard works as in forward(); "deferred" is treated
+    as "fallback", because the next step consumes this step's flow_low."""
+
+    def __init__(self, model, iters=12, warm_start=False, pad_mode="sintel"):
+        if model.training:
+            raise NotImplementedError(_TRAINING_MSG)
+        if model.__dict__.get("_is_replica", False) or model.__dict__.get("_dp_source") is not None:
+            raise RuntimeError("RAFT.stream(): a DataParallel replica lives for one forward; open the stream on "
+                               "the source module")
+        if int(iters) < 1:
+            raise ValueError(f"iters must be >= 1, got {iters}")
+        self.model, self.iters, self.warm_start = model, int(iters), bool(warm_start)
+        self.pad_mode = pad_mode
+        self.centred = pad_mode == "sintel"   # any other mode: rows at the bottom, as InputPadder
+        self.plan = None
+        self.layout = None          # (dtype tag, B, H, W) of the first frame
+        self.shape = None
+        self.primed = False
+        self.closed = False
+        self.last_flow_init = None
+        self._wkey = None
+        self._prev_low = None       # flow_low of the step before (warm start; survives a stale step)
+        self._inexact_prev = False  # the previous frame's feature map came from a step the guard flagged
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 (interpreter shutdown: the GPU context may already be gone)
+            pass
+
+    def pad(self, height, width):
+        """[left, right, top, bottom] this stream pads a height x width frame by (InputPadder._pad)."""
+        return frame_pad(height, width, self.centred)
+
+    def reset(self):
+        """Sequence boundary: the next frame primes the stream and returns None."""
+        self.primed = False
+        self.last_flow_init = None
+        self._prev_low = None
+        self._inexact_prev = False
+        if self.plan is not None:
+            with torch.cuda.device(self.plan.device):
+                self.plan.reset()
+
+    def close(self):
+        if self.closed:
+            return
+        self.closed = True
+        if self.plan is not None:
+            self.plan.release()
+            self.plan = None
+
+    def _build(self, device):
+        m = self.model
+        prec = m.resolved_precision()
+        pk = m.packed(device, prec)
+        self._wkey = m._weights_key()
+        tag, b, h, w = self.layout
+        return StreamPlan(pk, b, h, w, self.iters, dtype_tag=tag, centred=self.centred,
+                          alternate=bool(m.args.alternate_corr), warm_start=self.warm_start, device=device,
+                          range_guard=m.range_guard != "off")
+
+    def _step(self, frame):
+        pl = self.plan
+        pl.frame_in.copy_(frame)
+        if pl.guarded:
+            pl.range_flag.zero_()
+        if self.model.hip_graph and (pl.graph is not None or pl.runs > 0):
+            pl.replay()
+        else:
+            pl.run()
+
+    def push(self, frame):
+        if self.closed:
+            raise RuntimeError("FlowStream.push() after close()")
+        m = self.model
+        if m.training:
+            raise NotImplementedError(_TRAINING_MSG)
+        layout = frame_layout(frame)
+        device = next(m.parameters()).device
+        if frame.is_cuda and frame.device != device:
+            raise RuntimeError(f"the frame is on {frame.device}, the model on {device}")
+        if device.type != "cuda":
+            raise RuntimeError(f"raft_optical_flow_amd runs on a ROCm GPU only: the model is on {device}")
+        if self.layout is None:
+            self.layout, self.shape = layout, (frame.dtype, tuple(frame.shape))
+        elif (frame.dtype, tuple(frame.shape)) != self.shape:
+            raise ValueError(f"this stream was opened with {self.shape[0]} frames of shape {self.shape[1]}, got "
+                             f"{frame.dtype} {tuple(frame.shape)} (open another stream for another shape)")
+        with torch.cuda.device(device):
+            return self._push(frame, device)
+
+    def _push(self, frame, device):
+        m = self.model
+        if self.plan is None or (not self.primed and m._weights_key() != self._wkey):
+            if self.plan is not None:
+                torch.cuda.current_stream().synchronize()
+                self.plan.release()
+            self.plan = self._build(device)
+        pl = self.plan
+        if not self.primed:
+            pl.reset()
+            pl.frame_in.copy_(frame)
+            pl.prime()
+            self.primed = True
+            return None
+        # enqueue first, check the weights while the step runs (as forward() does)
+        self._step(frame)
+        if m._weights_key() != self._wkey:
+            # the weights changed since the plan was packed: the step that just ran is stale.  Rebuild,
+            # encode the held previous frame again with the new weights, and run the step again.
+            torch.cuda.current_stream().synchronize()
+            old = pl
+            pl = self.plan = self._build(device)
+            pl.prime(raw=old.raw_prev)
+            if self._prev_low is not None:
+                pl.flow_low.copy_(self._prev_low)
+            torch.cuda.current_stream().synchronize()
+            old.release()
+            self._step(frame)
+        return self._finish(pl)
+
+    def _finish(self, pl):
+        m = self.model
+        left, right, top, bottom = pl.pad
+        low = pl.flow_low.clone()
+        up = pl.flow_up[0][..., top:pl.Hp - bottom, left:pl.Wp - right].clone()
+        self.last_flow_init = pl.flow_init.clone() if self.warm_start else None
+        mode = m.range_guard
+        if pl.guarded and mode != "off":
+            raised = bool(int(pl.range_flag.item()))
+            if raised or self._inexact_prev:
+                msg = ("f16x3 range guard: an activation exceeded 2^15 in magnitude, outside the exact range "
+                       "of the split-f16 conv arithmetic")
+                if mode == "raise":
+                    raise FloatingPointError(msg)
+                warnings.warn(msg + "; this step was re-run with exact f32 MFMA convs", RuntimeWarning)
+                low, up_p = m.forward(pl.raw_prev, pl.raw_cur, self.iters, self.last_flow_init, True, True,
+                                      _prec="fp32")
+                up = up_p[..., top:pl.Hp - bottom, left:pl.Wp - right].clone()
+                pl.flow_low.copy_(low)  # the next warm start begins from the exact flow
+            # (a flagged step leaves this frame's feature map inexact: the next pair is re-run as well)
+            self._inexact_prev = raised
+        if self.warm_start:
+            self._prev_low = low.clone()
+        return low, up
 
 
 def _register_exit_check(model):

@@ -1,0 +1,1 @@
+from .utils import ingest_frame  # noqa: F401

@@ -8,6 +8,8 @@
                                                    coordinates (raft_bilinear_sample)
   coords_grid          :74-77                      (x, y) pixel grid
   upflow8              :80-82                      8 * bilinear x8 upsampling (raft_upflow8)
+  ingest_frame         (no reference counterpart)  InputPadder.pad + RAFT.forward's 2 * (x / 255) - 1
+                                                   of one video frame in one launch (raft_ingest_frame)
 
 Every helper computes on the GPU through the HIP kernels of libraft_hip.so; a CPU tensor is
 copied to the current GPU and the result copied back (there is no host computation path).
@@ -145,3 +147,23 @@ def upflow8(flow, mode="bilinear"):
     out = torch.empty(n, 2, 8 * h, 8 * w, device=flow.device)
     _lib().call("raft_upflow8", crow.data_ptr(), out.data_ptr(), n, h, w, K.stream_handle())
     return out.to(src.device)
+
+
+@_on_device
+def ingest_frame(frame, mode="sintel"):
+    """The front end of RAFT.stream on its own (raft_ingest_frame): a frame, float32 [B,3,H,W] in
+    0..255 or uint8 [B,H,W,3], replicate-padded as InputPadder(mode) pads it.  Returns
+    (rows, padded, pad): rows [B*Hp*Wp, 3] = 2 * (padded / 255) - 1 in NHWC order, padded the raw
+    float32 [B,3,Hp,Wp] frame, pad = InputPadder._pad ([left, right, top, bottom]).  The results
+    stay on the GPU."""
+    from .. import engine as E
+    tag, b, h, w = E.frame_layout(frame)
+    x = _on_gpu(frame).contiguous()
+    centred = mode == "sintel"
+    pad = E.frame_pad(h, w, centred)
+    hp, wp = h + pad[2] + pad[3], w + pad[0] + pad[1]
+    rows = torch.empty(b * hp * wp, 3, device=x.device)
+    padded = torch.empty(b, 3, hp, wp, device=x.device)
+    _lib().call("raft_ingest_frame", x.data_ptr(), tag, b, h, w, int(centred), rows.data_ptr(), padded.data_ptr(),
+                _stream())
+    return rows, padded, pad
