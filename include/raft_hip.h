@@ -545,6 +545,52 @@ int raft_ingest_frame(const void* in, int dtype, int B, int H, int W, int centre
 int raft_stream_carry(const float* fmap_cur, float* fmap_prev, size_t n_fmap, const float* rows_cur, float* rows_prev,
                       size_t n_rows, const float* raw_cur, float* raw_prev, size_t n_raw, raft_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * Bidirectional video streams (BidiStreamPlan / RAFT.stream(bidirectional=True)) and the
+ * forward-backward consistency check.  Additive entries: RAFT_HIP_ABI_VERSION stays 19.
+ * --------------------------------------------------------------------------- */
+/* The n-copy form of raft_stream_carry: up to RAFT_CARRY_MAX_SEGS pitched 2-D device copies in one
+ * launch (rows x cols floats each, row pitches src_ld / dst_ld >= cols; a flat copy is rows = 1).
+ * 16-byte accesses where every segment's pointers, cols and pitches allow them.  No segment may
+ * be in place; the segments must not overlap each other.  The segment array is read on the host. */
+#define RAFT_CARRY_MAX_SEGS 8
+typedef struct raft_copy2d {
+  const float* src;
+  long src_ld;
+  float* dst;
+  long dst_ld;
+  long rows, cols;
+} raft_copy2d;
+int raft_stream_carry_n(const raft_copy2d* segs, int n, raft_stream_t stream);
+
+/* Forward-backward consistency (the UnFlow criterion, Meister et al. 2018, published defaults
+ * alpha = 0.01, beta = 0.5), both directions and all B images in one launch.
+ *
+ * Definition.  For direction fw at pixel x = (j, i) of the H x W frame, F = flow_fw, G = flow_bw
+ * (channel 0 = x displacement, channel 1 = y displacement, in pixels):
+ *   p = x + F(x)                                   the pixel's target in the other frame
+ *   p not finite, or outside [0, W-1] x [0, H-1]:  err = +inf, occ = 1 (the pixel left the frame)
+ *   otherwise:  g   = bilinear sample of G at p; corners at floor(p) and floor(p) + 1; a +1 corner
+ *                     that falls outside the frame has weight 0 and is not read
+ *               err = |F(x) + g|^2
+ *               occ = err > alpha * (|F(x)|^2 + |g|^2) + beta
+ * and occ = 1 wherever err is not finite (a NaN or inf of G reached it).  Direction bw is the same
+ * with F and G swapped.  (Sign convention: the sample is taken at x + F(x), where the pixel goes.)
+ * The sampling position is taken as floor(j + Fx) = j + floor(Fx) with weight Fx - floor(Fx) (exact in
+ * fp32 but for one rounding of <= 2^-25 where -1 < Fx < 0; j + Fx itself is never rounded); the
+ * blend, err and the threshold round once per operation (no contraction).
+ *
+ * Layout.  A flow is float32 NCHW with unit element stride: element (b, c, y, x) of the FRAME is
+ * at flow[b * batch_stride + c * chan_stride + (top + y) * pitch + left + x] (strides in floats):
+ * a crop at (top, left) of a larger, pitched buffer, e.g. the stream's padded [2B][2][Hp][Wp]
+ * flow_up in place; a plain tensor is top = left = 0, pitch = W.  A target in the buffer's
+ * padding is outside the frame.  occ_* are uint8 [B][H][W] (0 / 1), err_* float32 [B][H][W],
+ * dense; err_* 16-byte and occ_* 4-byte aligned.  B * H * W < 2^30. */
+int raft_fb_consistency(const float* flow_fw, long fw_batch_stride, long fw_chan_stride, long fw_pitch,
+                        const float* flow_bw, long bw_batch_stride, long bw_chan_stride, long bw_pitch, int top,
+                        int left, int B, int H, int W, float alpha, float beta, unsigned char* occ_fw,
+                        unsigned char* occ_bw, float* err_fw, float* err_bw, raft_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("RAFT_HIP_LIB") or os.path.join(_HERE, "libraft_hip.so
 c_int = ctypes.c_int
 c_float = ctypes.c_float
 c_size_t = ctypes.c_size_t
+c_long = ctypes.c_long
 c_void_p = ctypes.c_void_p
 c_char_p = ctypes.c_char_p
 P = c_void_p  # device pointers are passed as integers / void*
@@ -68,6 +69,15 @@ class ConvParams(ctypes.Structure):
         ("in_norm", P), ("in_norm_relu", c_int),
         ("weight_s", P),
     ]
+
+
+CARRY_MAX_SEGS = 8   # RAFT_CARRY_MAX_SEGS
+
+
+class Copy2D(ctypes.Structure):
+    """Mirror of `raft_copy2d` (include/raft_hip.h): one pitched 2-D copy of raft_stream_carry_n."""
+
+    _fields_ = [("src", P), ("src_ld", c_long), ("dst", P), ("dst_ld", c_long), ("rows", c_long), ("cols", c_long)]
 
 
 CONV_KERNEL_HALO = 1
@@ -184,6 +194,9 @@ _PROTOS = {
     "raft_frame_pad": (None, [c_int, c_int, c_int] + [ctypes.POINTER(c_int)] * 4),
     "raft_ingest_frame": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, P]),
     "raft_stream_carry": (c_int, [P, P, c_size_t, P, P, c_size_t, P, P, c_size_t, P]),
+    "raft_stream_carry_n": (c_int, [P, c_int, P]),
+    "raft_fb_consistency": (c_int, [P, c_long, c_long, c_long, P, c_long, c_long, c_long, c_int, c_int, c_int, c_int,
+                                    c_int, c_float, c_float, P, P, P, P, P]),
 }
 
 EXPORTED = tuple(_PROTOS)

@@ -7,7 +7,8 @@ launches with their fixed pointers.  `RaftPlan.run()` replays the launch list
 on the current stream; `RaftPlan.capture()` records it into a hipGraph
 (torch.cuda.CUDAGraph on ROCm) so the 32-iteration refinement loop replays
 with no host work per kernel.  `StreamPlan` (at the end of the module) is the
-same for a video: one frame per step, every frame encoded once (RAFT.stream).
+same for a video: one frame per step, every frame encoded once (RAFT.stream);
+`BidiStreamPlan` adds the backward flow and the forward-backward check.
 
 Buffer layout of the recurrent state (P = B * H/8 * W/8 rows), RAFT-full:
   HX   [P, 384]  = h (128) | motion conv (126) | flow (2) | inp (128)
@@ -1025,3 +1026,128 @@ class StreamPlan:
 
     def kernel_names(self):
         return [l.name for l in self.launches if isinstance(l, Launch)]
+
+
+def carry_launch(segs, side=False) -> Launch:
+    """raft_stream_carry_n over [(src, src_ld, dst, dst_ld, rows, cols)] (tensors; counts in floats)."""
+    assert 0 < len(segs) <= _lib.CARRY_MAX_SEGS, len(segs)
+    arr = (_lib.Copy2D * len(segs))()
+    for a, (src, sld, dst, dld, rows, cols) in zip(arr, segs):
+        a.src, a.src_ld, a.dst, a.dst_ld, a.rows, a.cols = src.data_ptr(), sld, dst.data_ptr(), dld, rows, cols
+    return Launch("raft_stream_carry_n", arr, len(segs), keep=(arr, segs), side=side)
+
+
+class BidiStreamPlan(StreamPlan):
+    """StreamPlan with both directions of every pair and their forward-backward consistency check: the
+    refinement runs at batch 2B = [prev -> cur (B images); cur -> prev (B images)], and every frame still
+    passes through the feature network AND the context network once.
+
+    Feature maps live in three slots [prev | cur | prev] of one buffer, so fmap1 = slots[0:2] and
+    fmap2 = slots[1:3] are both contiguous batches of 2B and the correlation build, the lookups and the
+    update block run unmodified.  The context of the backward pair is cnet(cur), which is also the context
+    of the NEXT forward pair: it is computed on `cur` (not `prev`) into the second half of the 2B context
+    buffers and carried to the first half one step later.  The GRU overwrites its hidden state in place,
+    so cnet's `net` output has a buffer of its own (net0) that is copied into HX's h slot ahead of the
+    loop.  (`inp` itself is read by the context GEMMs only, so it is not carried.)  One step:
+
+      raft_stream_carry_n  fmap cur -> slots 0 and 2, raw cur -> raw prev, net0 and the context
+                           terms: second half -> first half
+      raft_ingest_frame    the staged frame -> cur rows + cur raw frame
+      FORK
+        main: fnet trunk + head on cur (n_img = B) -> slot 1, then the correlation build (or the alternate
+              path's fmap2 pooling) at batch 2B
+        side: cnet + the GRU context terms on cur's rows -> second halves; warm start:
+              raft_forward_interpolate at batch 2B (each direction from its own flow_low)
+      JOIN
+      raft_stream_carry_n  net0 [2P, hdim] -> HX's h slot
+      raft_init_coords ... raft_flow_from_coords, plan_refinement at batch 2B
+      raft_fb_consistency  flow_up [2B,2,Hp,Wp] in place (crop offsets = the padding) -> occ, err
+
+    `prime()` is ingest + fnet + cnet + the context terms of the first frame."""
+
+    def __init__(self, *args, fb_alpha=0.01, fb_beta=0.5, **kw):
+        self.fb_alpha, self.fb_beta = float(fb_alpha), float(fb_beta)
+        super().__init__(*args, **kw)
+
+    def _build(self, pk, B, iters, alternate, device):
+        A = self.arena = Arena(device)
+        H, W, Hp, Wp = self.H, self.W, self.Hp, self.Wp
+        h, w = Hp // 8, Wp // 8
+        self.h, self.w = h, w
+        P = B * h * w
+        pu = pk.update
+        hd = pu.hdim
+        if self.dtype_tag == _lib.FRAME_U8_NHWC:
+            self.frame_in = torch.empty(B, H, W, 3, dtype=torch.uint8, device=device)
+        else:
+            self.frame_in = torch.empty(B, 3, H, W, device=device)
+        self.rows_cur = A.rows(B * Hp * Wp, 3)
+        self.raw_prev, self.raw_cur = (torch.empty(B, 3, Hp, Wp, device=device) for _ in range(2))
+        self.fmaps = A.rows(3 * P, pk.fdim)              # [prev | cur | prev]
+        self.fmap_cur = self.fmaps[P:2 * P]
+        fmap1, fmap2 = self.fmaps[:2 * P], self.fmaps[P:]
+        self.flow_init = torch.zeros(2 * B, 2, h, w, device=device) if self.warm_start else None
+        self.flow_low = torch.zeros(2 * B, 2, h, w, device=device)
+        ub = self.ub = UpdateBuffers(A, pu, 2 * P, pk.levels * (2 * pk.radius + 1) ** 2)
+        self.net0 = A.rows(2 * P, hd)                    # cnet's tanh half: the GRU's initial hidden state
+        self.inp = A.rows(P, pu.cdim)                    # cnet's relu half of cur
+        # (one tensor per direction: each base is aligned for the kernel's 16-byte stores at any H * W)
+        self.occ = [torch.zeros(B, 1, H, W, dtype=torch.uint8, device=device) for _ in range(2)]
+        self.err = [torch.zeros(B, 1, H, W, device=device) for _ in range(2)]
+        nf = P * pk.fdim
+        segs = [(self.fmap_cur, nf, self.fmaps[:P], nf, 1, nf), (self.fmap_cur, nf, self.fmaps[2 * P:], nf, 1, nf),
+                (self.raw_cur, self.raw_cur.numel(), self.raw_prev, self.raw_cur.numel(), 1, self.raw_cur.numel()),
+                (self.net0[P:], P * hd, self.net0[:P], P * hd, 1, P * hd)]
+        segs += [(c[P:], P * 3 * hd, c[:P], P * 3 * hd, 1, P * 3 * hd) for c in ub.ctx]
+        carry = carry_launch(segs)
+        self._ingest = Launch("raft_ingest_frame", self.frame_in.data_ptr(), self.dtype_tag, B, H, W, int(self.centred),
+                              self.rows_cur.data_ptr(), self.raw_cur.data_ptr())
+        F = self._fnet = []
+        x, fh_, fw_ = plan_encoder_trunk(F, A, pk.fnet, Rows(self.rows_cur), B, Hp, Wp)
+        assert (fh_, fw_) == (h, w), ((fh_, fw_), (h, w))
+        _conv(F, pk.fnet.head, x, B, h, w, Rows(self.fmap_cur))
+        # context network of the CURRENT frame: image1 of the backward pair now and of the forward pair
+        # one step later (core/raft.py:193-200)
+        C = self._cnet = []
+        xc, _, _ = plan_encoder_trunk(C, A, pk.cnet, Rows(self.rows_cur), B, Hp, Wp)
+        _conv(C, pk.cnet.head, xc, B, h, w, Rows(self.net0[P:]), epilogue=_lib.EPI_TANH_RELU, split=pk.hdim,
+              out1=Rows(self.inp))
+        for (zr, q, ctx), buf in zip(pu.gru, ub.ctx):
+            _conv(C, ctx, Rows(self.inp), B, h, w, Rows(buf[P:]), epilogue=_lib.EPI_LINEAR)
+        self.prime_launches = [self._ingest] + F + C     # (run without a side stream: in order)
+        L = self.launches = [carry, self._ingest, K.FORK] + F
+        plan_correlation(self, L, A, pk, 2 * B, h, w, fmap1, fmap2, alternate)
+        n_ctx = len(L)
+        L.extend(C)
+        if self.warm_start:
+            L.append(Launch("raft_forward_interpolate", self.flow_low.data_ptr(), self.flow_init.data_ptr(), 2 * B, h,
+                            w))
+        for l in L[n_ctx:]:
+            l.side = True
+        L.append(K.JOIN)
+        L.append(carry_launch([(self.net0, hd, ub.hx, pu.ld, 2 * P, hd)]))
+        plan_refinement(self, L, pk, ub, 2 * B, Hp, Wp, iters, True, alternate, fmap1, device)
+        up = self.flow_up[0]
+        half = B * 2 * Hp * Wp
+        L.append(Launch("raft_fb_consistency", up.data_ptr(), 2 * Hp * Wp, Hp * Wp, Wp, up.data_ptr() + 4 * half,
+                        2 * Hp * Wp, Hp * Wp, Wp, self.pad[2], self.pad[0], B, H, W, self.fb_alpha, self.fb_beta,
+                        self.occ[0].data_ptr(), self.occ[1].data_ptr(), self.err[0].data_ptr(),
+                        self.err[1].data_ptr()))
+
+    def _state(self):
+        P = self.B * self.h * self.w
+        return [self.fmap_cur, self.raw_cur, self.flow_low, self.net0[P:]] + [c[P:] for c in self.ub.ctx]
+
+    def prime(self, raw=None):
+        if raw is None:
+            K.run(self.prime_launches)
+            return
+        _lib.call("raft_ingest_frame", raw.data_ptr(), _lib.FRAME_F32_NCHW, self.B, self.Hp, self.Wp, 1,
+                  self.rows_cur.data_ptr(), self.raw_cur.data_ptr(), K.stream_handle())
+        K.run(self._fnet + self._cnet)
+
+    def release(self):
+        super().release()
+        self._cnet = []
+        for name in ("fmaps", "net0", "inp", "occ", "err"):
+            setattr(self, name, None)

@@ -22,6 +22,9 @@ evaluate.py's many KITTI sizes do not accumulate device memory.
 
 Video: `model.stream(iters, warm_start, pad_mode)` returns a FlowStream (below): `push(frame)`
 gives the flow of (previous frame, this frame) and encodes every frame once (engine.StreamPlan).
+With `bidirectional=True` it also gives the flow of (this frame, previous frame) and the
+forward-backward occlusion masks of the two, still at one fnet and one cnet pass per frame
+(engine.BidiStreamPlan).
 
 f16x3 range guard: the default fp32-accurate split arithmetic holds only while every
 conv input stays below 65504 in magnitude (include/raft_hip.h).  The convs and lookups
@@ -47,7 +50,7 @@ import atexit
 import os
 import warnings
 import weakref
-from collections import OrderedDict, deque
+from collections import OrderedDict, deque, namedtuple
 
 import threading
 
@@ -55,10 +58,10 @@ import torch
 import torch.nn as nn
 
 from . import kernels as K
-from .engine import PackedRaft, RaftPlan, StreamPlan, frame_layout, frame_pad
+from .engine import BidiStreamPlan, PackedRaft, RaftPlan, StreamPlan, frame_layout, frame_pad
 from .extractor import BasicEncoder, SmallEncoder
 from .update import BasicUpdateBlock, SmallUpdateBlock
-from .utils.utils import coords_grid
+from .utils.utils import check_fb_params, coords_grid, fb_consistency
 
 # module attribute kept for API parity with core/raft.py:11-22 (callers monkeypatch it);
 # the HIP path never autocasts: its arithmetic is RAFT.conv_precision
@@ -356,14 +359,27 @@ class RAFT(nn.Module):
         return outs
 
 
-    def stream(self, iters=12, warm_start=False, pad_mode="sintel"):
+    def stream(self, iters=12, warm_start=False, pad_mode="sintel", bidirectional=False, fb_alpha=0.01, fb_beta=0.5):
         """A FlowStream over consecutive video frames: `push(frame)` returns (flow_low, flow_up) of
-        (previous frame, this frame), and every frame passes through the feature network once."""
-        return FlowStream(self, iters, warm_start, pad_mode)
+        (previous frame, this frame), and every frame passes through the feature network once.
+        bidirectional=True: push returns a BidirectionalFlow (both directions, their occlusion masks and
+        forward-backward residuals; fb_alpha / fb_beta are the check's constants, utils.fb_consistency)."""
+        return FlowStream(self, iters, warm_start, pad_mode, bidirectional, fb_alpha, fb_beta)
 
 
 _TRAINING_MSG = ("raft_optical_flow_amd.RAFT is an inference path: call model.eval() "
                  "(training / BatchNorm batch statistics are out of scope)")
+
+
+BidirectionalFlow = namedtuple("BidirectionalFlow", ["low_fw", "up_fw", "low_bw", "up_bw", "occ_fw", "occ_bw",
+                                                     "err_fw", "err_bw"])
+BidirectionalFlow.__doc__ = """What FlowStream.push returns with bidirectional=True.
+
+  low_fw, up_fw    [B,2,h,w], [B,2,H,W] float32  flow previous -> current frame (the one-directional result)
+  low_bw, up_bw    same                          flow current -> previous frame
+  occ_fw, occ_bw   [B,1,H,W] bool                True where the direction's flow fails the forward-backward check
+  err_fw, err_bw   [B,1,H,W] float32             the squared residual the masks were thresholded from
+(utils.fb_consistency(up_fw, up_bw, fb_alpha, fb_beta) of the same step, computed inside the step.)"""
 
 
 class FlowStream:
@@ -376,6 +392,12 @@ class FlowStream:
       s.close()             # releases graph and buffers (also at garbage collection / `with` exit)
       s.last_flow_init      # [B,2,h,w] the last step started from (None when warm_start=False)
 
+    bidirectional=True: push returns a BidirectionalFlow instead (both flows, occlusion masks, residuals);
+    it equals model(cat[pad(prev), pad(cur)], cat[pad(cur), pad(prev)], iters, flow_init=s.last_flow_init,
+    test_mode=True) + unpad, with last_flow_init [2B,2,h,w], the forward half first; a warm start begins each
+    direction from forward_interpolate of its own direction's flow of the step before.  The masks are
+    utils.fb_consistency of the unpadded flows: a target in the padding is outside the frame.
+
     A frame is float32 [B,3,H,W] in 0..255 or uint8 [B,H,W,3], of any size (it is replicate-padded as
     InputPadder(pad_mode) does; flow_up comes back at the frame's own size, flow_low at 1/8 of the
     padded one); B > 1 is B independent streams in lockstep.  The first push fixes shape and dtype.
@@ -387,7 +409,8 @@ class FlowStream:
     release_plans() do not see it).  The range guard works as in forward(); "deferred" is treated
     as "fallback", because the next step consumes this step's flow_low."""
 
-    def __init__(self, model, iters=12, warm_start=False, pad_mode="sintel"):
+    def __init__(self, model, iters=12, warm_start=False, pad_mode="sintel", bidirectional=False, fb_alpha=0.01,
+                 fb_beta=0.5):
         if model.training:
             raise NotImplementedError(_TRAINING_MSG)
         if model.__dict__.get("_is_replica", False) or model.__dict__.get("_dp_source") is not None:
@@ -395,6 +418,10 @@ class FlowStream:
                                "the source module")
         if int(iters) < 1:
             raise ValueError(f"iters must be >= 1, got {iters}")
+        if not isinstance(bidirectional, bool):
+            raise TypeError(f"bidirectional must be a bool, got {type(bidirectional).__name__}")
+        self.bidirectional = bidirectional
+        self.fb_alpha, self.fb_beta = check_fb_params(fb_alpha, fb_beta)
         self.model, self.iters, self.warm_start = model, int(iters), bool(warm_start)
         self.pad_mode = pad_mode
         self.centred = pad_mode == "sintel"   # any other mode: rows at the bottom, as InputPadder
@@ -449,9 +476,11 @@ class FlowStream:
         pk = m.packed(device, prec)
         self._wkey = m._weights_key()
         tag, b, h, w = self.layout
-        return StreamPlan(pk, b, h, w, self.iters, dtype_tag=tag, centred=self.centred,
-                          alternate=bool(m.args.alternate_corr), warm_start=self.warm_start, device=device,
-                          range_guard=m.range_guard != "off")
+        kw = dict(dtype_tag=tag, centred=self.centred, alternate=bool(m.args.alternate_corr),
+                  warm_start=self.warm_start, device=device, range_guard=m.range_guard != "off")
+        if self.bidirectional:
+            return BidiStreamPlan(pk, b, h, w, self.iters, fb_alpha=self.fb_alpha, fb_beta=self.fb_beta, **kw)
+        return StreamPlan(pk, b, h, w, self.iters, **kw)
 
     def _step(self, frame):
         pl = self.plan
@@ -519,6 +548,9 @@ class FlowStream:
         low = pl.flow_low.clone()
         up = pl.flow_up[0][..., top:pl.Hp - bottom, left:pl.Wp - right].clone()
         self.last_flow_init = pl.flow_init.clone() if self.warm_start else None
+        bidi, B = self.bidirectional, pl.B
+        if bidi:
+            occ, err = [o.view(torch.bool).clone() for o in pl.occ], [e.clone() for e in pl.err]
         mode = m.range_guard
         if pl.guarded and mode != "off":
             raised = bool(int(pl.range_flag.item()))
@@ -528,14 +560,21 @@ class FlowStream:
                 if mode == "raise":
                     raise FloatingPointError(msg)
                 warnings.warn(msg + "; this step was re-run with exact f32 MFMA convs", RuntimeWarning)
-                low, up_p = m.forward(pl.raw_prev, pl.raw_cur, self.iters, self.last_flow_init, True, True,
-                                      _prec="fp32")
+                i1, i2 = pl.raw_prev, pl.raw_cur
+                if bidi:
+                    i1, i2 = torch.cat([i1, i2]), torch.cat([i2, i1])
+                low, up_p = m.forward(i1, i2, self.iters, self.last_flow_init, True, True, _prec="fp32")
                 up = up_p[..., top:pl.Hp - bottom, left:pl.Wp - right].clone()
+                if bidi:  # the masks of the exact flows
+                    o_fw, o_bw, e_fw, e_bw = fb_consistency(up[:B], up[B:], self.fb_alpha, self.fb_beta)
+                    occ, err = [o_fw, o_bw], [e_fw, e_bw]
                 pl.flow_low.copy_(low)  # the next warm start begins from the exact flow
             # (a flagged step leaves this frame's feature map inexact: the next pair is re-run as well)
             self._inexact_prev = raised
         if self.warm_start:
             self._prev_low = low.clone()
+        if bidi:
+            return BidirectionalFlow(low[:B], up[:B], low[B:], up[B:], occ[0], occ[1], err[0], err[1])
         return low, up
 
 

@@ -1,1 +1,1 @@
-from .utils import ingest_frame  # noqa: F401
+from .utils import fb_consistency, ingest_frame  # noqa: F401

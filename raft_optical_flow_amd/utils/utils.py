@@ -10,6 +10,8 @@
   upflow8              :80-82                      8 * bilinear x8 upsampling (raft_upflow8)
   ingest_frame         (no reference counterpart)  InputPadder.pad + RAFT.forward's 2 * (x / 255) - 1
                                                    of one video frame in one launch (raft_ingest_frame)
+  fb_consistency       (no reference counterpart)  forward-backward consistency of a flow pair: occlusion
+                                                   masks and squared residuals (raft_fb_consistency)
 
 Every helper computes on the GPU through the HIP kernels of libraft_hip.so; a CPU tensor is
 copied to the current GPU and the result copied back (there is no host computation path).
@@ -147,6 +149,61 @@ def upflow8(flow, mode="bilinear"):
     out = torch.empty(n, 2, 8 * h, 8 * w, device=flow.device)
     _lib().call("raft_upflow8", crow.data_ptr(), out.data_ptr(), n, h, w, K.stream_handle())
     return out.to(src.device)
+
+
+def check_fb_params(alpha, beta):
+    """(alpha, beta) of the forward-backward check as floats: finite and not negative."""
+    import math
+    for name, v in (("alpha", alpha), ("beta", beta)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise TypeError(f"fb_consistency: {name} must be a number, got {type(v).__name__}")
+        if not math.isfinite(v) or v < 0:
+            raise ValueError(f"fb_consistency: {name} must be finite and not negative, got {v}")
+    return float(alpha), float(beta)
+
+
+def fb_consistency(flow_fw, flow_bw, alpha=0.01, beta=0.5):
+    """Forward-backward consistency of a flow pair (raft_fb_consistency, one launch for both directions).
+
+    flow_fw [B,2,H,W] maps frame 1 to frame 2, flow_bw frame 2 to frame 1: float32 GPU tensors, any strides
+    (crops of larger tensors are read in place).  For direction fw, F = flow_fw, G = flow_bw, at pixel x:
+    p = x + F(x); p not finite or outside [0, W-1] x [0, H-1]: err = +inf, occ = True; otherwise
+    g = bilinear G(p), err = |F(x) + g|^2, occ = err > alpha (|F(x)|^2 + |g|^2) + beta (the UnFlow criterion
+    with its published defaults; include/raft_hip.h has the full definition).  Direction bw swaps F and G.
+    Returns (occ_fw, occ_bw, err_fw, err_bw): bool and float32 [B,1,H,W]."""
+    for name, t in (("flow_fw", flow_fw), ("flow_bw", flow_bw)):
+        if not torch.is_tensor(t):
+            raise TypeError(f"fb_consistency: {name} must be a tensor, got {type(t).__name__}")
+        if t.dtype != torch.float32:
+            raise TypeError(f"fb_consistency: {name} must be float32, got {t.dtype}")
+        if t.dim() != 4 or t.shape[1] != 2 or t.numel() == 0:
+            raise ValueError(f"fb_consistency: {name} must be [B, 2, H, W], got {tuple(t.shape)}")
+    if flow_fw.shape != flow_bw.shape:
+        raise ValueError(f"fb_consistency: the flows differ in shape: {tuple(flow_fw.shape)} / {tuple(flow_bw.shape)}")
+    alpha, beta = check_fb_params(alpha, beta)
+    for name, t in (("flow_fw", flow_fw), ("flow_bw", flow_bw)):
+        if not t.is_cuda:
+            raise RuntimeError(f"fb_consistency runs on a ROCm GPU only: {name} is on {t.device} (no CPU path)")
+    if flow_fw.device != flow_bw.device:
+        raise RuntimeError(f"fb_consistency: the flows are on {flow_fw.device} and {flow_bw.device}")
+    b, _, h, w = flow_fw.shape
+    if b * h * w >= 1 << 30:
+        raise ValueError(f"fb_consistency: {b} x {h} x {w} pixels exceed 2^30")
+
+    def view(t):
+        # unit element stride and a row pitch that holds a row; anything else (a transposed or expanded
+        # view) is copied once
+        if t.stride(3) != 1 and w > 1 or (h > 1 and t.stride(2) < w):
+            t = t.contiguous()
+        return t, (t.stride(0), t.stride(1), t.stride(2) if h > 1 else w)
+
+    with torch.cuda.device(flow_fw.device):
+        (fw, sfw), (bw, sbw) = view(flow_fw), view(flow_bw)
+        occ = [torch.empty(b, 1, h, w, dtype=torch.uint8, device=fw.device) for _ in range(2)]
+        err = [torch.empty(b, 1, h, w, device=fw.device) for _ in range(2)]
+        _lib().call("raft_fb_consistency", fw.data_ptr(), *sfw, bw.data_ptr(), *sbw, 0, 0, b, h, w, alpha, beta,
+                    occ[0].data_ptr(), occ[1].data_ptr(), err[0].data_ptr(), err[1].data_ptr(), _stream())
+    return occ[0].view(torch.bool), occ[1].view(torch.bool), err[0], err[1]
 
 
 @_on_device
