@@ -591,6 +591,65 @@ int raft_fb_consistency(const float* flow_fw, long fw_batch_stride, long fw_chan
                         int left, int B, int H, int W, float alpha, float beta, unsigned char* occ_fw,
                         unsigned char* occ_bw, float* err_fw, float* err_bw, raft_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * Flow colour-wheel visualisation (core/utils/flow_viz.py on the device; utils.flow_viz,
+ * RAFT.stream(visualize=...)).  Additive entries: RAFT_HIP_ABI_VERSION stays 19.
+ * --------------------------------------------------------------------------- */
+/* A flow field as a colour image: hue = direction, saturation = magnitude (the Middlebury coding of
+ * Baker et al., "A Database and Evaluation Methodology for Optical Flow", ICCV 2007).
+ *
+ * Definition.  (u, v) = channels 0 and 1 of the flow at a pixel of image b; arithmetic is fp32 and
+ * every written operation rounds once (no contraction), division and sqrt correctly rounded.
+ *   clip     with RAFT_VIZ_CLIP: u = min(max(u, 0), clip_flow), v likewise, before everything else
+ *            (a NaN stays a NaN; +inf becomes clip_flow, -inf becomes 0).  The LOWER bound 0 is the
+ *            reference's (np.clip(flow_uv, 0, clip_flow)): it removes every negative component.
+ *            It is kept for parity.
+ *   black    u or v not finite (after the clip): the pixel is (0, 0, 0) and takes no part in the
+ *            maximum.  (The reference casts a NaN to uint8 there, which is undefined: this rule is
+ *            this library's own.)
+ *   rad_max  per image b: the maximum of sqrt(u*u + v*v) over the image's pixels that are not black;
+ *            0 if there are none.  fixed_rad_max > 0 replaces it for all images (one scale for a
+ *            whole video: colours do not flicker with each frame's own maximum).  (A finite flow
+ *            whose square overflows fp32 gives rad_max = +inf: every u' and v' is 0, a white image.)
+ *   scale    u' = u / (rad_max + 1e-5f), v' = v / (rad_max + 1e-5f).  With RAFT_VIZ_UNIT: u' = u,
+ *            v' = v (flow_uv_to_colors: no maximum, no epsilon; fixed_rad_max is not read).
+ *   wheel    rad = sqrt(u'*u' + v'*v'),  a = atan2(-v', -u') / pi,  fk = (a + 1) / 2 * 54,
+ *            k0 = floor(fk) clamped to [0, 54],  k1 = (k0 + 1) mod 55,  f = fk - k0;
+ *            per channel c:  col = (1 - f) * (wheel[k0][c] / 255) + f * (wheel[k1][c] / 255),
+ *            col = rad <= 1 ? 1 - rad * (1 - col) : 0.75 * col,  byte = floor(255 * col).
+ *   wheel[55][3]: six segments of n = 15, 6, 4, 11, 13, 6 entries through red, yellow, green, cyan,
+ *            blue, magenta and back to red.  Entry i of a segment is the segment's first colour with
+ *            one channel moved by t = floor(255 * i / n): G = t (red-yellow), R = 255 - t
+ *            (yellow-green), B = t (green-cyan), G = 255 - t (cyan-blue), R = t (blue-magenta),
+ *            B = 255 - t (magenta-red).
+ * Stacking (demo.py's np.concatenate([img, flo], axis=0)).  With frame != NULL the output has 2H rows
+ * per image: rows 0..H-1 are the frame (float32 NCHW, 3 channels, 0..255, the crop offsets of the
+ * flow and strides of its own): each value rounded to nearest (ties to even), saturated to 0..255,
+ * NaN -> 0, so an integer-valued frame passes through exactly; rows H..2H-1 are the colours.
+ *
+ * Layout.  The flow is raft_fb_consistency's: float32 NCHW with unit element stride, element
+ * (b, c, y, x) at flow[b * batch_stride + c * chan_stride + (top + y) * pitch + left + x] (strides
+ * in floats), so the stream's padded [B][2][Hp][Wp] flow_up is read in place; a plain tensor is
+ * top = left = 0, pitch = W.  Nothing outside the crop is read.  out is uint8 [B][H][W][3] (or
+ * [B][2H][W][3]), dense, 4-byte aligned, channel order R, G, B, or B, G, R with RAFT_VIZ_BGR (frame
+ * rows included).  out may not alias flow, frame or ws.  B * H * W < 2^30.
+ *
+ * Launches.  Without a fixed scale: one launch writes each work-group's maximum to ws
+ * (raft_flow_viz_ws_bytes(B, H, W) bytes, 4-byte aligned; every float of it is written before it is
+ * read, so it needs no initialisation), and the colour launch's work-groups reduce their images'
+ * partial maxima before colouring.  No atomics, no buffer zeroed between calls: a captured call
+ * replays to identical bytes.  With fixed_rad_max > 0 or RAFT_VIZ_UNIT only the colour launch runs
+ * and ws may be NULL. */
+#define RAFT_VIZ_BGR 1  /* bytes in B, G, R order */
+#define RAFT_VIZ_UNIT 2 /* no normalisation (u' = u, v' = v) */
+#define RAFT_VIZ_CLIP 4 /* clip both components to [0, clip_flow] first */
+/* bytes of raft_flow_to_rgb's workspace; 0 for sizes it rejects */
+size_t raft_flow_viz_ws_bytes(int B, int H, int W);
+int raft_flow_to_rgb(const float* flow, long batch_stride, long chan_stride, long pitch, int top, int left, int B,
+                     int H, int W, float clip_flow, float fixed_rad_max, int flags, const float* frame,
+                     long frame_batch_stride, long frame_chan_stride, long frame_pitch, float* ws,
+                     unsigned char* out, raft_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

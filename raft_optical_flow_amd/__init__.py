@@ -7,7 +7,7 @@ and the alt_cuda_corr plugin module; the compute runs in libraft_hip.so
 """
 from .corr import AlternateCorrBlock, CorrBlock  # noqa: F401
 from .extractor import BasicEncoder, SmallEncoder  # noqa: F401
-from .raft import RAFT, BidirectionalFlow, FlowStream  # noqa: F401
+from .raft import RAFT, BidirectionalFlow, BidirectionalFlowViz, FlowStream, FlowViz  # noqa: F401
 from .update import BasicUpdateBlock, SmallUpdateBlock  # noqa: F401
 from .utils.utils import InputPadder, coords_grid, fb_consistency, ingest_frame, upflow8  # noqa: F401
 

@@ -36,6 +36,10 @@ RANGE_LIMIT = 32768.0  # RAFT_RANGE_LIMIT: |x| above it raises the f16x3 range g
 FRAME_F32_NCHW = 0   # raft_ingest_frame input: float32 [B, 3, H, W]
 FRAME_U8_NHWC = 1    # uint8 [B, H, W, 3]
 
+VIZ_BGR = 1    # raft_flow_to_rgb flags: bytes in B, G, R order
+VIZ_UNIT = 2   # no normalisation (flow_uv_to_colors)
+VIZ_CLIP = 4   # clip both components to [0, clip_flow] first
+
 EPI_LINEAR = 0
 EPI_RELU = 1
 EPI_RESID_RELU = 2
@@ -197,6 +201,9 @@ _PROTOS = {
     "raft_stream_carry_n": (c_int, [P, c_int, P]),
     "raft_fb_consistency": (c_int, [P, c_long, c_long, c_long, P, c_long, c_long, c_long, c_int, c_int, c_int, c_int,
                                     c_int, c_float, c_float, P, P, P, P, P]),
+    "raft_flow_viz_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "raft_flow_to_rgb": (c_int, [P, c_long, c_long, c_long, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_int,
+                                 P, c_long, c_long, c_long, P, P, P]),
 }
 
 EXPORTED = tuple(_PROTOS)

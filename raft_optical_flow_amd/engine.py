@@ -894,15 +894,18 @@ class StreamPlan:
               (flow_low of the step before -> flow_init)
       JOIN
       raft_init_coords ... raft_flow_from_coords, plan_refinement as RaftPlan's
+      raft_flow_to_rgb    (visualize only) flow_up [B,2,Hp,Wp] in place (crop offsets = the padding) -> uint8
+                          [B,H,W,3], with viz_stack under the pair's image1 (the `prev` raw frame)
 
     The carry opens the step instead of closing it, so that after a step BOTH raw frames of its pair
     are still in the plan: the range guard's exact re-run and a rebuild after a weight change read
     them.  `prime()` (the first frame after a reset) is the short list ingest + fnet."""
 
     def __init__(self, pk: PackedRaft, B, H, W, iters, dtype_tag=_lib.FRAME_F32_NCHW, centred=True, alternate=False,
-                 warm_start=False, device=None, range_guard=True):
+                 warm_start=False, device=None, range_guard=True, visualize=None, viz_rad_max=None, viz_stack=False):
         self.pk, self.B, self.H, self.W, self.iters = pk, B, H, W, iters
         self.dtype_tag, self.centred, self.alternate, self.warm_start = dtype_tag, bool(centred), alternate, warm_start
+        self.visualize, self.viz_rad_max, self.viz_stack = visualize, viz_rad_max, bool(viz_stack)
         self.test_mode = True
         self.device = device
         self.pad = frame_pad(H, W, centred)
@@ -960,6 +963,24 @@ class StreamPlan:
             l.side = True
         L.append(K.JOIN)
         plan_refinement(self, L, pk, ub, B, Hp, Wp, iters, True, alternate, self.fmap_prev, device)
+        self.rgb = [self._plan_viz(L, self.flow_up[0], self.raw_prev)] if self.visualize else None
+
+    def _plan_viz(self, L, up, frame):
+        """Append raft_flow_to_rgb (its maximum launch, skipped with a fixed viz_rad_max, and its colour launch)
+        on B images of the padded flow `up` [B,2,Hp,Wp], read in place with the padding as crop offsets; with
+        viz_stack above the raw padded `frame` [B,3,Hp,Wp] cropped likewise.  Returns the uint8 output."""
+        B, H, W, Hp, Wp = self.B, self.H, self.W, self.Hp, self.Wp
+        dev = up.device
+        rgb = torch.zeros(B, 2 * H if self.viz_stack else H, W, 3, dtype=torch.uint8, device=dev)
+        ws = None
+        if self.viz_rad_max is None:
+            ws = torch.zeros(_lib.load().raft_flow_viz_ws_bytes(B, H, W) // 4, device=dev)
+        fr = frame if self.viz_stack else None
+        L.append(Launch("raft_flow_to_rgb", up.data_ptr(), 2 * Hp * Wp, Hp * Wp, Wp, self.pad[2], self.pad[0], B, H, W,
+                        0.0, self.viz_rad_max or 0.0, _lib.VIZ_BGR if self.visualize == "bgr" else 0,
+                        fr.data_ptr() if fr is not None else None, 3 * Hp * Wp, Hp * Wp, Wp,
+                        ws.data_ptr() if ws is not None else None, rgb.data_ptr(), keep=(up, fr, ws, rgb)))
+        return rgb
 
     # -- state --------------------------------------------------------------
     def reset(self):
@@ -1020,7 +1041,7 @@ class StreamPlan:
         self.launches, self.prime_launches, self._fnet, self._ingest = [], [], [], None
         self.arena.bufs.clear()
         for name in ("pyramid", "corr_ws", "f2levels", "ub", "frame_in", "rows_prev", "rows_cur", "raw_prev", "raw_cur",
-                     "fmap_prev", "fmap_cur", "flow_init", "flow_low", "flow_up", "range_flag"):
+                     "fmap_prev", "fmap_cur", "flow_init", "flow_low", "flow_up", "range_flag", "rgb"):
             if hasattr(self, name):
                 setattr(self, name, None)
 
@@ -1062,6 +1083,7 @@ class BidiStreamPlan(StreamPlan):
       raft_stream_carry_n  net0 [2P, hdim] -> HX's h slot
       raft_init_coords ... raft_flow_from_coords, plan_refinement at batch 2B
       raft_fb_consistency  flow_up [2B,2,Hp,Wp] in place (crop offsets = the padding) -> occ, err
+      raft_flow_to_rgb     (visualize only) once per direction
 
     `prime()` is ingest + fnet + cnet + the context terms of the first frame."""
 
@@ -1133,6 +1155,10 @@ class BidiStreamPlan(StreamPlan):
                         2 * Hp * Wp, Hp * Wp, Wp, self.pad[2], self.pad[0], B, H, W, self.fb_alpha, self.fb_beta,
                         self.occ[0].data_ptr(), self.occ[1].data_ptr(), self.err[0].data_ptr(),
                         self.err[1].data_ptr()))
+        # one call per direction: each normalises by its own maximum and stacks its own image1 (forward: the
+        # previous frame, backward: the current one), and each output has an aligned base of its own
+        self.rgb = [self._plan_viz(L, up[:B], self.raw_prev), self._plan_viz(L, up[B:], self.raw_cur)] \
+            if self.visualize else None
 
     def _state(self):
         P = self.B * self.h * self.w

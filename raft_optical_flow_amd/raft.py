@@ -61,6 +61,7 @@ from . import kernels as K
 from .engine import BidiStreamPlan, PackedRaft, RaftPlan, StreamPlan, frame_layout, frame_pad
 from .extractor import BasicEncoder, SmallEncoder
 from .update import BasicUpdateBlock, SmallUpdateBlock
+from .utils.flow_viz import check_viz_options, flow_to_rgb
 from .utils.utils import check_fb_params, coords_grid, fb_consistency
 
 # module attribute kept for API parity with core/raft.py:11-22 (callers monkeypatch it);
@@ -359,12 +360,17 @@ class RAFT(nn.Module):
         return outs
 
 
-    def stream(self, iters=12, warm_start=False, pad_mode="sintel", bidirectional=False, fb_alpha=0.01, fb_beta=0.5):
+    def stream(self, iters=12, warm_start=False, pad_mode="sintel", bidirectional=False, fb_alpha=0.01, fb_beta=0.5,
+               visualize=None, viz_rad_max=None, viz_stack=False):
         """A FlowStream over consecutive video frames: `push(frame)` returns (flow_low, flow_up) of
         (previous frame, this frame), and every frame passes through the feature network once.
         bidirectional=True: push returns a BidirectionalFlow (both directions, their occlusion masks and
-        forward-backward residuals; fb_alpha / fb_beta are the check's constants, utils.fb_consistency)."""
-        return FlowStream(self, iters, warm_start, pad_mode, bidirectional, fb_alpha, fb_beta)
+        forward-backward residuals; fb_alpha / fb_beta are the check's constants, utils.fb_consistency).
+        visualize="rgb" / "bgr": the step also colours flow_up on the device (utils.flow_viz.flow_to_rgb) and
+        push returns a FlowViz (or a BidirectionalFlowViz); viz_rad_max fixes the colour scale for the whole
+        video, viz_stack puts the pair's first frame above the colours as demo.py does."""
+        return FlowStream(self, iters, warm_start, pad_mode, bidirectional, fb_alpha, fb_beta, visualize, viz_rad_max,
+                          viz_stack)
 
 
 _TRAINING_MSG = ("raft_optical_flow_amd.RAFT is an inference path: call model.eval() "
@@ -382,6 +388,18 @@ BidirectionalFlow.__doc__ = """What FlowStream.push returns with bidirectional=T
 (utils.fb_consistency(up_fw, up_bw, fb_alpha, fb_beta) of the same step, computed inside the step.)"""
 
 
+FlowViz = namedtuple("FlowViz", ["flow_low", "flow_up", "rgb"])
+FlowViz.__doc__ = """What FlowStream.push returns with visualize set: (flow_low, flow_up) as without it, and
+rgb uint8 [B,H,W,3] ([B,2H,W,3] with viz_stack; B, G, R order with visualize="bgr"):
+utils.flow_viz.flow_to_rgb(flow_up, viz_rad_max, frame=the previous frame) of the same step, computed inside
+the step."""
+
+BidirectionalFlowViz = namedtuple("BidirectionalFlowViz", BidirectionalFlow._fields + ("rgb_fw", "rgb_bw"))
+BidirectionalFlowViz.__doc__ = """BidirectionalFlow's fields, then rgb_fw and rgb_bw: the colour images of up_fw and
+up_bw (FlowViz.rgb).  Each is normalised by its own maximum unless viz_rad_max is given; with viz_stack rgb_fw
+lies under the previous frame and rgb_bw under the current one (each direction's image1)."""
+
+
 class FlowStream:
     """Optical flow over a video, one frame per call (RAFT.stream).
 
@@ -391,6 +409,12 @@ class FlowStream:
       s.reset()             # sequence boundary
       s.close()             # releases graph and buffers (also at garbage collection / `with` exit)
       s.last_flow_init      # [B,2,h,w] the last step started from (None when warm_start=False)
+
+    visualize="rgb" / "bgr": push returns a FlowViz (flow_low, flow_up, rgb) instead: rgb is the colour-wheel image of
+    flow_up, uint8 [B,H,W,3], coloured inside the step (utils.flow_viz.flow_to_rgb of the same flow, bit for bit).
+    viz_rad_max=None normalises every image by its own maximum, as the reference's flow_to_image does; a positive
+    number fixes the scale so that colours do not flicker from frame to frame.  viz_stack=True puts the pair's
+    first frame above the colours ([B,2H,W,3], demo.py's layout).
 
     bidirectional=True: push returns a BidirectionalFlow instead (both flows, occlusion masks, residuals);
     it equals model(cat[pad(prev), pad(cur)], cat[pad(cur), pad(prev)], iters, flow_init=s.last_flow_init,
@@ -410,7 +434,11 @@ class FlowStream:
     as "fallback", because the next step consumes this step's flow_low."""
 
     def __init__(self, model, iters=12, warm_start=False, pad_mode="sintel", bidirectional=False, fb_alpha=0.01,
-                 fb_beta=0.5):
+                 fb_beta=0.5, visualize=None, viz_rad_max=None, viz_stack=False):
+        self.visualize, self.viz_rad_max = check_viz_options(visualize, viz_rad_max)
+        if not isinstance(viz_stack, bool):
+            raise TypeError(f"viz_stack must be a bool, got {type(viz_stack).__name__}")
+        self.viz_stack = viz_stack
         if model.training:
             raise NotImplementedError(_TRAINING_MSG)
         if model.__dict__.get("_is_replica", False) or model.__dict__.get("_dp_source") is not None:
@@ -477,7 +505,8 @@ class FlowStream:
         self._wkey = m._weights_key()
         tag, b, h, w = self.layout
         kw = dict(dtype_tag=tag, centred=self.centred, alternate=bool(m.args.alternate_corr),
-                  warm_start=self.warm_start, device=device, range_guard=m.range_guard != "off")
+                  warm_start=self.warm_start, device=device, range_guard=m.range_guard != "off",
+                  visualize=self.visualize, viz_rad_max=self.viz_rad_max, viz_stack=self.viz_stack)
         if self.bidirectional:
             return BidiStreamPlan(pk, b, h, w, self.iters, fb_alpha=self.fb_alpha, fb_beta=self.fb_beta, **kw)
         return StreamPlan(pk, b, h, w, self.iters, **kw)
@@ -551,6 +580,7 @@ class FlowStream:
         bidi, B = self.bidirectional, pl.B
         if bidi:
             occ, err = [o.view(torch.bool).clone() for o in pl.occ], [e.clone() for e in pl.err]
+        rgb = [t.clone() for t in pl.rgb] if self.visualize else None
         mode = m.range_guard
         if pl.guarded and mode != "off":
             raised = bool(int(pl.range_flag.item()))
@@ -568,14 +598,20 @@ class FlowStream:
                 if bidi:  # the masks of the exact flows
                     o_fw, o_bw, e_fw, e_bw = fb_consistency(up[:B], up[B:], self.fb_alpha, self.fb_beta)
                     occ, err = [o_fw, o_bw], [e_fw, e_bw]
+                if self.visualize:  # the colours of the exact flows (backward: under the current frame)
+                    crop = (Ellipsis, slice(top, pl.Hp - bottom), slice(left, pl.Wp - right))
+                    rgb = [flow_to_rgb(up[k * B:(k + 1) * B], self.viz_rad_max, None, self.visualize == "bgr",
+                                       fr[crop] if self.viz_stack else None)
+                           for k, fr in enumerate((pl.raw_prev, pl.raw_cur)[:2 if bidi else 1])]
                 pl.flow_low.copy_(low)  # the next warm start begins from the exact flow
             # (a flagged step leaves this frame's feature map inexact: the next pair is re-run as well)
             self._inexact_prev = raised
         if self.warm_start:
             self._prev_low = low.clone()
         if bidi:
-            return BidirectionalFlow(low[:B], up[:B], low[B:], up[B:], occ[0], occ[1], err[0], err[1])
-        return low, up
+            out = BidirectionalFlow(low[:B], up[:B], low[B:], up[B:], occ[0], occ[1], err[0], err[1])
+            return BidirectionalFlowViz(*out, *rgb) if self.visualize else out
+        return FlowViz(low, up, rgb[0]) if self.visualize else (low, up)
 
 
 def _register_exit_check(model):
