@@ -113,6 +113,11 @@ __global__ void convex_upsample_kernel(const float* coords, const float* mask, i
 
 // upflow8 (core/utils/utils.py:80-82): 8 * bilinear(align_corners=True)
 __global__ void upflow8_kernel(const float* coords, float* out, int B, int H, int W) {
+  // the reference's interpolate is separate fp32 multiplies and adds.  Contracted, lx = fma(sx, X, -x0) takes
+  // the unrounded product while x0 comes from the rounded one, which moved the result off the reference's
+  // float32 by half an ulp of rx times the flow's slope (4e-4 px at 30 x 240, 8e-3 px at 363 x 363 on a rough
+  // field); uncontracted it is the reference's float32 bit for bit (tests/test_gpu_upsample.py).
+#pragma clang fp contract(off)
   const int H8 = 8 * H, W8 = 8 * W;
   const long P8 = (long)H8 * W8;
   const float sy = H8 > 1 ? (float)(H - 1) / (float)(H8 - 1) : 0.f;

@@ -94,7 +94,10 @@ def forward_interpolate(flow):
     """Warm-start flow for the next frame pair (evaluate.py:37-41): each pixel takes the flow of
     the nearest point the flow moves a pixel to, over the points that land strictly inside the
     frame (scipy griddata 'nearest' in the reference; 0 where none lands).  flow [2, H, W] (or
-    [B, 2, H, W]) -> float32, same shape, same device."""
+    [B, 2, H, W]) -> float32, same shape, same device.
+    Where several such points are at exactly the same smallest distance the one with the lowest source
+    index (row-major) is taken; scipy's choice on exact ties is implementation-defined, so only there can
+    the result differ from the reference's."""
     f = _on_gpu(flow.detach()).float().contiguous()
     batched = f.dim() == 4
     if not batched:
