@@ -126,7 +126,15 @@ int raft_corr_pyramid_level(const float* pyramid, int B, int H, int W, int num_l
  * flow_out (optional, may be NULL): NHWC rows [B*H*W][flow_ld] receive
  *      coords - coords_grid (the RAFT loop's `flow`, core/raft.py:222).
  * range_flag (optional, may be NULL): set to 1 when an output exceeds RAFT_RANGE_LIMIT in
- *      magnitude (see the f16x3 range guard below). */
+ *      magnitude (see the f16x3 range guard below).
+ * Any fp32 coordinate is accepted and no address depends on it unchecked.  A tap's sample
+ * position is computed in fp32 as the reference does (x / 2^l + offset, 2 X / (W_l - 1) - 1,
+ * back through (g + 1) / 2 * (W_l - 1)): a tap whose position is finite but far off the map is
+ * 0 (grid_sample's zero padding), however far (1e6, 3e9, past the int range); a tap whose
+ * position on either axis is not finite (a NaN or infinite coordinate, |2 X| overflowing fp32,
+ * or a 1-px level, W_l - 1 = 0) is NaN, as the reference's.  Other pixels are unaffected.
+ * flow_out is coords - coords_grid in fp32 whatever the coordinate.  The same holds for
+ * raft_corr_lookup_convf1 and raft_corr_lookup_conv. */
 int raft_corr_lookup(const float* pyramid, int B, int H, int W, int num_levels, int radius,
                      const float* coords, int coords_layout, float* out, int out_ld, int out_layout,
                      float* flow_out, int flow_ld, int* range_flag, raft_stream_t stream);

@@ -985,8 +985,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void c
   // axis on the VALU.  (The builtin, not an inline-asm v_readfirstlane: issued right behind
   // the v_cvt that wrote its operand, the asm version read a stale value on gfx950 -- the
   // hazard recognizer does not look into asm -- and fetched wrong tiles.)
-  const int xf = __builtin_amdgcn_readfirstlane((int)floorf(x));
-  const int yf = __builtin_amdgcn_readfirstlane((int)floorf(y));
+  const int xf = __builtin_amdgcn_readfirstlane(floor_origin(x));
+  const int yf = __builtin_amdgcn_readfirstlane(floor_origin(y));
 #pragma unroll
   for (int k = 0; k < LMAX; ++k) {
     const int x0 = (xf >> k) - R;
@@ -1054,7 +1054,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void c
     axis_entry<R>(x * s, xf >> l, ix, wm1, rw, xw, xt, xi);
     int yi;
     float yt;
-    axis_entry<R>(y * s, yf >> l, ix, hm1, rh, yw, yt, yi);
+    axis_entry<R, true>(y * s, yf >> l, ix, hm1, rh, yw, yt, yi);
     // .x: the row's byte offset in the patch (row * RS * 4), or the negative OFF_PATCH / NAN_POS code
     if (col) ytab[wv][lane] = int4{yw >= 0 ? yw * RS * 4 : yw, __float_as_int(yt), __float_as_int(1.0f - yt), yi};
   }

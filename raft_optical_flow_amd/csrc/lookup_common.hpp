@@ -58,6 +58,17 @@ __device__ __forceinline__ float div_rn(float a, float b, float rcp) {
   return fmaf(r, rcp, q);
 }
 
+// floor(c) of a level-0 coordinate as the integer every level's window origin is shifted from,
+// clamped to +-2^30.  In range it is floor(c); beyond, the window lies off every map either way,
+// and the clamp keeps the window arithmetic built on it (origin - R, + 2R + 2, the differences of
+// the clipped row / column intervals) from wrapping: unclamped, a row coordinate at or past the int
+// range (+-3e9, +-inf: the conversion saturates) wrapped the scalar-interval form's row count
+// back to 2R + 2 and its window base ~2^29 tile rows off the pyramid, a fetch from unmapped
+// memory.  (v_med3_f32: one VALU op; NaN gives a bound, and the tap is NaN by axis_entry.)
+__device__ __forceinline__ int floor_origin(float c) {
+  return (int)__builtin_amdgcn_fmed3f(floorf(c), -1073741824.0f, 1073741824.0f);
+}
+
 // One-axis sampling entry of offset d at level l.  The window's x and y
 // sample positions are separable — tap (ix, iy) samples x-entry ix and
 // y-entry iy — so the reference's per-tap coordinate arithmetic runs on
@@ -65,12 +76,23 @@ __device__ __forceinline__ float div_rn(float a, float b, float rcp) {
 //   w: i - patch origin when i and i + 1 lie on the staged patch; OFF_PATCH
 //      when the float round trip moved the floor off it; NAN_POS when the
 //      position is not finite (a 1-px level: W - 1 = 0)
+// What is staged differs by axis.  Columns: the whole 4-aligned tile range covering
+// floor(c) - R .. floor(c) + R + 1 (a lane's 16-B load brings a tile row's four columns).  Rows
+// (ROW): only the window's own 2R + 2 rows floor(c) - R .. floor(c) + R + 1 -- the other rows of
+// the patch's tile rows are not fetched and hold zeros, so a y-entry the round trip moved one row
+// outside the window is OFF_PATCH even where that row lies in the same tile.  (Tested against the
+// tile range like the columns, it read the unfetched row as zeros and lost that row's corners:
+// up to 33 x 2^-24 x |corner| at ~3 % of integer coordinates.)
 constexpr int OFF_PATCH = -1000000;
 constexpr int NAN_POS = -2000000;
 
 // (fc = floor(c), computed by the caller: an integer shift of the wave's level-0 floor)
-template <int R>
+template <int R, bool ROW = false>
 __device__ __forceinline__ void axis_entry(float c, int fc, int d, float m1, float rcp, int& w, float& t, int& i) {
+  // every operation rounds as written (the fmaf calls of div_rn stay fused): contracted, t = u - f0
+  // came from the unrounded product u = (g + 1) * (m1 / 2) in some instantiations and not in others,
+  // as the compiler chose -- up to 2^-21 off the reference's fraction at u ~ 10
+#pragma clang fp contract(off)
   constexpr int WD = 2 * R + 2;
   const int v0 = fc - R;
   const int o = (v0 >> 2) * 4;                               // patch origin on this axis
@@ -83,7 +105,8 @@ __device__ __forceinline__ void axis_entry(float c, int fc, int d, float m1, flo
   t = u - f0;
   i = (int)f0;
   const int ww = i - o;
-  w = !fin ? NAN_POS : (ww >= 0 && ww + 1 < ext) ? ww : OFF_PATCH;
+  const bool on = ROW ? (unsigned)(i - v0) < (unsigned)(WD - 1) : (ww >= 0 && ww + 1 < ext);
+  w = !fin ? NAN_POS : on ? ww : OFF_PATCH;
 }
 
 // LDS patch of one wave: element (row r, column c) of level l at

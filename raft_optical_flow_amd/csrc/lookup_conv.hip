@@ -284,7 +284,7 @@ __global__ __launch_bounds__(512) void lookup_conv_kernel(LookupConvArgs g) {
         twl = il == l ? ltw[l] : twl;
         msl = il == l ? lmsz4[l] : msl;
       }
-      const int wx0 = ((int)floorf(fx) >> il) - R, wy0 = ((int)floorf(fy) >> il) - R;
+      const int wx0 = (floor_origin(fx) >> il) - R, wy0 = (floor_origin(fy) >> il) - R;
       const int tyo = wy0 >> 2, txo = wx0 >> 2;
       const int ntx = ((wx0 + WD - 1) >> 2) - txo + 1;
       const int rlo = max(wy0, 0), rhi = min(wy0 + WD, 4 * thl);
@@ -313,8 +313,8 @@ __global__ __launch_bounds__(512) void lookup_conv_kernel(LookupConvArgs g) {
 #pragma unroll
     for (int k = 0; k < LC_PX; ++k) {
       const unsigned gp = (unsigned)px_gp[k];
-      const int xf = __builtin_amdgcn_readfirstlane((int)floorf(px_x[k]));
-      const int yf = __builtin_amdgcn_readfirstlane((int)floorf(px_y[k]));
+      const int xf = __builtin_amdgcn_readfirstlane(floor_origin(px_x[k]));
+      const int yf = __builtin_amdgcn_readfirstlane(floor_origin(px_y[k]));
 #pragma unroll
       for (int l = 0; l < LC_L; ++l) {
         const int wx0 = (xf >> l) - R, wy0 = (yf >> l) - R;
@@ -361,7 +361,7 @@ __global__ __launch_bounds__(512) void lookup_conv_kernel(LookupConvArgs g) {
         msl = il == l ? lmsz[l] : msl;
         bsl = il == l ? lbs[l] : bsl;
       }
-      const int wx0 = ((int)floorf(fx) >> il) - R, wy0 = ((int)floorf(fy) >> il) - R;
+      const int wx0 = (floor_origin(fx) >> il) - R, wy0 = (floor_origin(fy) >> il) - R;
       const int tyo = wy0 >> 2, txo = wx0 >> 2;
       const int ntx = ((wx0 + WD - 1) >> 2) - txo + 1;
       const int rlo = max(wy0, 0), rhi = min(wy0 + WD, 4 * thl);
@@ -397,8 +397,8 @@ __global__ __launch_bounds__(512) void lookup_conv_kernel(LookupConvArgs g) {
   for (int k = 0; k < LC_PX; ++k) {
     const bool ok = px_ok[k];
     const int gp = px_gp[k];
-    const int xf = __builtin_amdgcn_readfirstlane((int)floorf(px_x[k]));
-    const int yf = __builtin_amdgcn_readfirstlane((int)floorf(px_y[k]));
+    const int xf = __builtin_amdgcn_readfirstlane(floor_origin(px_x[k]));
+    const int yf = __builtin_amdgcn_readfirstlane(floor_origin(px_y[k]));
 #pragma unroll
     for (int l = 0; l < LC_L; ++l) {
       const int wx0 = (xf >> l) - R, wy0 = (yf >> l) - R;
@@ -431,12 +431,12 @@ __global__ __launch_bounds__(512) void lookup_conv_kernel(LookupConvArgs g) {
 #pragma unroll
   for (int k = 0; k < LC_PX; ++k) {
     const float s = __builtin_ldexpf(1.0f, -l);
-    const int xf = __builtin_amdgcn_readfirstlane((int)floorf(px_x[k]));
-    const int yf = __builtin_amdgcn_readfirstlane((int)floorf(px_y[k]));
+    const int xf = __builtin_amdgcn_readfirstlane(floor_origin(px_x[k]));
+    const int yf = __builtin_amdgcn_readfirstlane(floor_origin(px_y[k]));
     axis_entry<R>(px_x[k] * s, xf >> l, ix, prm[0], prm[1], xw[k], xt[k], xi[k]);
     int yw, yi;
     float yt;
-    axis_entry<R>(px_y[k] * s, yf >> l, ix, prm[2], prm[3], yw, yt, yi);
+    axis_entry<R, true>(px_y[k] * s, yf >> l, ix, prm[2], prm[3], yw, yt, yi);
     onp[k] = xw[k] >= 0 && yw >= 0;
     if (col) ytab[k * LC_L * RD + lane] = int4{yw >= 0 ? yw * RS * 4 : yw, __float_as_int(yt), __float_as_int(1.0f - yt), yi};
   }

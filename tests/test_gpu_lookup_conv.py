@@ -31,6 +31,30 @@ def t(x):
     return torch.from_numpy(np.ascontiguousarray(x)).float().to(DEV)
 
 
+def pack_lookup_conv_weights(wc, bc, wf, bf, prec):
+    """raft_corr_lookup_conv's weight operands from convc1's [256, 324] / convf1's [128, 2, 7, 7]
+    fp32 weights (numpy), packed as the engine does: returns (pc, frag, pf, ffrag), the packed convs
+    (their .bias is the launch's bias) and the fragment-order weights."""
+    from raft_optical_flow_amd import _lib
+    from raft_optical_flow_amd import kernels as K
+    p = _lib.PRECISIONS[prec]
+    # convc1 weights, packed as the engine does (engine.convc1_frag_weight)
+    pc = K.pack_conv(torch.from_numpy(wc)[:, :, None, None], torch.from_numpy(bc), 1, 0, device=DEV)
+    pc.precision = p
+    split = pc.launch_weight()
+    n_pad, k_pad = split.shape
+    frag = torch.empty(int(_lib.load().raft_lookup_conv_weight_floats(256, k_pad)), device=DEV)
+    _lib.call("raft_lookup_conv_pack_weight", split.data_ptr(), n_pad, k_pad, 256, frag.data_ptr(), K.stream_handle())
+    # convf1 weights, packed as the engine does (GATHER mode, K = 2 (dy*7 + dx) + ci)
+    pf = K.pack_conv(torch.from_numpy(wf), torch.from_numpy(bf), 1, 3, mode=_lib.RAFT_CONV_GATHER, device=DEV)
+    pf.precision = p
+    fsplit = pf.launch_weight()
+    fnp, fkp = fsplit.shape
+    ffrag = torch.empty(int(_lib.load().raft_lookup_conv_weight_floats(128, fkp)), device=DEV)
+    _lib.call("raft_lookup_conv_pack_weight", fsplit.data_ptr(), fnp, fkp, 128, ffrag.data_ptr(), K.stream_handle())
+    return pc, frag, pf, ffrag
+
+
 def _case(B, h, w, prec, coord_sigma=3.0, fscale=1.0, seed=5, C=64):
     from raft_optical_flow_amd import _lib
     from raft_optical_flow_amd import kernels as K
@@ -48,25 +72,12 @@ def _case(B, h, w, prec, coord_sigma=3.0, fscale=1.0, seed=5, C=64):
     coords = (grid + rng.normal(0, coord_sigma, (B, h, w, 2))).astype(np.float32)
     cr = t(coords.reshape(-1, 2))
     P, ntap = B * h * w, 324
-    # convc1 weights, packed as the engine does (engine.convc1_frag_weight)
     wc = (rng.standard_normal((256, ntap)) * 0.05).astype(np.float32)
     bc = (rng.standard_normal(256) * 0.1).astype(np.float32)
-    pc = K.pack_conv(torch.from_numpy(wc)[:, :, None, None], torch.from_numpy(bc), 1, 0, device=DEV)
-    pc.precision = p
-    split = pc.launch_weight()
-    n_pad, k_pad = split.shape
-    frag = torch.empty(int(_lib.load().raft_lookup_conv_weight_floats(256, k_pad)), device=DEV)
-    _lib.call("raft_lookup_conv_pack_weight", split.data_ptr(), n_pad, k_pad, 256, frag.data_ptr(), K.stream_handle())
-    # convf1 weights, packed as the engine does (GATHER mode, K = 2 (dy*7 + dx) + ci)
     wf = (rng.standard_normal((128, 2, 7, 7)) * 0.1).astype(np.float32)
     bf = (rng.standard_normal(128) * 0.1).astype(np.float32)
     rnd = {"f16": torch.float16, "bf16": torch.bfloat16}.get(prec)
-    pf = K.pack_conv(torch.from_numpy(wf), torch.from_numpy(bf), 1, 3, mode=_lib.RAFT_CONV_GATHER, device=DEV)
-    pf.precision = p
-    fsplit = pf.launch_weight()
-    fnp, fkp = fsplit.shape
-    ffrag = torch.empty(int(_lib.load().raft_lookup_conv_weight_floats(128, fkp)), device=DEV)
-    _lib.call("raft_lookup_conv_pack_weight", fsplit.data_ptr(), fnp, fkp, 128, ffrag.data_ptr(), K.stream_handle())
+    pc, frag, pf, ffrag = pack_lookup_conv_weights(wc, bc, wf, bf, prec)
     # unfused: lookup (+flow), convf1 alone
     corr = torch.full((P, ntap), -7.0, device=DEV)
     flow_a = torch.zeros(P, 4, device=DEV)

@@ -331,12 +331,12 @@ def test_lookup_window_forms_bit_equal():
         assert torch.equal(full[s], half)
 
 
-def _lookup_convf1_case(B, h, w, r, prec, coord_scale=1.0, seed=11):
+def _lookup_convf1_case(B, h, w, r, prec, coord_scale=1.0, seed=11, L=4):
     """raft_corr_lookup_convf1 vs raft_corr_lookup + an fp64 torch conv of the flow."""
     from raft_optical_flow_amd import _lib
     from raft_optical_flow_amd import kernels as K
     rng = np.random.default_rng(seed)
-    C, L = 64, 4
+    C = 64
     f1 = rng.standard_normal((B, C, h, w)).astype(np.float32)
     f2 = rng.standard_normal((B, C, h, w)).astype(np.float32)
     r1, r2 = K.nchw_to_rows(t(f1)), K.nchw_to_rows(t(f2))
@@ -402,6 +402,17 @@ def test_lookup_convf1_equals_lookup_and_conv(B, h, w, r, prec):
     from raft_optical_flow_amd import _lib
     p = {"f16x3": _lib.PREC_F16X3, "f16": _lib.PREC_F16, "bf16": _lib.PREC_BF16}[prec]
     flag, _ = _lookup_convf1_case(B, h, w, r, p)
+    assert flag == 0
+
+
+@pytest.mark.parametrize("B,h,w,r,L", [(2, 17, 21, 1, 4), (2, 17, 21, 2, 4), (1, 64, 72, 4, 6), (1, 64, 72, 1, 6),
+                                       (2, 17, 21, 2, 2)])
+def test_lookup_convf1_more_instantiations(B, h, w, r, L):
+    """The F1 instantiations the shapes above leave out: R = 1 and 2, the 6-level (LMAX = 6) kernel and
+    fewer than 4 levels; the lookup outputs stay bit-identical to raft_corr_lookup's, which
+    test_gpu_lookup_forms.py compares with the oracle at the same (R, LMAX)."""
+    from raft_optical_flow_amd import _lib
+    flag, _ = _lookup_convf1_case(B, h, w, r, _lib.PREC_F16X3, L=L)
     assert flag == 0
 
 
