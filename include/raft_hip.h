@@ -366,7 +366,21 @@ typedef struct raft_conv2d_params {
  * Only for convs with the linear epilogue (alpha 1, no add0) and more than 4 outputs (VEC) that run
  * on the halo, stem or (since round 5: the strided encoder convs) 64x64-tile GEMM kernel, whose
  * tiles then hold one image's rows each: raft_conv2d_stats_slots returns slots_per_image for such a
- * conv and 0 otherwise (raft_conv2d then rejects stats_part). */
+ * conv and 0 otherwise (raft_conv2d then rejects stats_part).
+ *
+ * Slot footprints (s = the slot within image b; y, x output coordinates, out_h x out_w per image):
+ *   halo  spatial tiles of TH = raft_conv2d_halo_tile_rows (8 or 16) rows x 16 columns, row-major:
+ *         tile t = (y / TH) * ceil(out_w / 16) + x / 16; slots_per_image = 4 * tiles; s = 4 t + w, wave w
+ *         holding tile rows (TH / 4) w .. (TH / 4)(w + 1) - 1 (two image rows x 16 columns per 32-pixel
+ *         block; at TH = 16 a wave's two blocks are combined by Chan's formula in fp32 before the write);
+ *   stem  the same with TH = 8 (tiles of 8 rows x 16 columns, s = 4 t + w, wave w rows 2w, 2w + 1);
+ *   GEMM  the image's out_h * out_w pixels in row-major order, 64 per tile (the last tile ragged):
+ *         slots_per_image = 2 * ceil(out_h * out_w / 64); s = 2 * tile + half, half h holding pixels
+ *         64 * tile + 32 h .. + 31.
+ * Every slot of every image is written for every n < N: the pixels of a footprint that lie outside the
+ * image are not counted, and a slot without a pixel holds (0, 0, 0).  The fourth float of an entry is
+ * written too (its value is unspecified); nothing else of stats_part is touched, columns
+ * N .. stats_ld - 1 in particular. */
 int raft_conv2d_stats_slots(const raft_conv2d_params* p);
 /* Tile rows of the halo kernel's launch of this conv: 8 (128-pixel tiles), 16 (the multi-round
  * 256-pixel tiles), 0 when the halo kernel does not run it (inspection / tests). */
@@ -404,12 +418,22 @@ int raft_conv2d_pair_form(const raft_conv2d_params* p0, const raft_conv2d_params
 /* 1 when the conv can apply its input's InstanceNorm in its loaders (in_norm above: the halo
  * kernel's 3x3 convs over <= 256 channels), else 0. */
 int raft_conv2d_in_norm_ok(const raft_conv2d_params* p);
+/* The merges: stats[(b * C + c) * 2 + {0, 1}] = {mean, 1 / sqrt(M2 / count + eps)} of the pooled
+ * partials part[((b * slots_per_image + s) * stats_ld + c) * 4 + {0, 1, 2}] = (count, mean, M2), s <
+ * slots_per_image, c < C <= stats_ld (columns C .. stats_ld - 1 are not read).  A slot with count 0 is
+ * skipped; it must hold finite mean and M2 (the convs write zeros).  Precondition of all three: slot 0
+ * of every image holds pixels (count > 0), as every conv above guarantees (slot 0 covers pixel (0, 0));
+ * raft_instnorm_merge_ws / _fused centre their sums on slot 0's mean.
+ * raft_instnorm_merge: Chan's formula in double, fixed order (deterministic). */
 int raft_instnorm_merge(const float* part, int slots_per_image, int B, int C, int stats_ld, float eps,
                         float* stats, raft_stream_t stream);
-/* raft_instnorm_merge over many slots, spread over the CUs: level 1 sums groups of 32 slots per
- * channel relative to slot 0's mean (coalesced 1-KiB slot rows, no division), level 2 combines the
- * groups in order (deterministic).  ws: raft_instnorm_merge_ws_floats(slots_per_image, B, C) floats,
- * 8-byte aligned; the same {mean, rstd} as raft_instnorm_merge to double rounding. */
+/* raft_instnorm_merge over many slots, spread over the CUs: level 1 sums groups of 64 slots per
+ * channel relative to K = slot 0's mean (coalesced 1-KiB slot rows, no division): n = sum c_i,
+ * s1 = sum c_i (m_i - K), s2 = sum M2_i + c_i (m_i - K)^2, in double; level 2 combines the groups in
+ * order (deterministic, wave w of 16 the groups w, w + 16, ... in batches of 8): mean = K + s1 / n,
+ * M2 = max(s2 - s1 * s1 / n, 0).  ws: raft_instnorm_merge_ws_floats(slots_per_image, B, C) floats,
+ * 8-byte aligned; the same {mean, rstd} as raft_instnorm_merge to double rounding (of sums whose
+ * size grows with the distance of K from the pooled mean). */
 size_t raft_instnorm_merge_ws_floats(int slots_per_image, int B, int C);
 int raft_instnorm_merge_ws(const float* part, int slots_per_image, int B, int C, int stats_ld, float eps, void* ws,
                            float* stats, raft_stream_t stream);

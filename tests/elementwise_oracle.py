@@ -224,3 +224,177 @@ def forward_interpolate_lowest(flow):
     src = flow.reshape(2, -1)
     out = np.where(lowest[None, :] >= 0, src[:, np.maximum(lowest, 0)], np.float32(0))
     return out.reshape(flow.shape).astype(np.float32)
+
+
+# ----------------------------------------------------------------------------- encoder InstanceNorm from the convs
+#
+# include/raft_hip.h, raft_conv2d_stats_slots ("Slot footprints") and the raft_instnorm_merge* comments, restated
+# in torch (any device): which output pixels each statistics slot holds, the (count, mean, M2) partials by their
+# definition in fp64, the documented float32 algorithm (per slot an fp32 sum, the mean, M2 about that mean; Chan's
+# merge in fp64), the pooled statistics by definition, and the comparisons the GPU tests assert with
+# (tests/test_encoder_norm_host.py holds these to each other and shows that the comparisons reject wrong references).
+
+STATS_EPS = 1e-5
+# The bounds of the merged statistics on the GPU: 4 x the largest error of the float32 restatement below against
+# fp64 over every ENC_TABLE shape, precision-independent data condition and image (measured by
+# test_encoder_norm_host.py::test_restated_statistics_against_fp64, recorded in DESIGN.md): the mean relative to
+# the channel's max |v| in its image, rstd relative.  Measured: E_mean 5.61e-7 (the constant channel on 16-row
+# tiles: 64 equal float32 values summed in a row round the same way at every step), E_rstd 3.51e-7 (the channel
+# whose bias is 30 deviations, 1x1 8 -> 32 at 2 x 10 x 14); rounded up here.  Bounds: 2.28e-6 and 1.44e-6.
+ENC_STATS_MEASURED = {"mean": 5.7e-7, "rstd": 3.6e-7}
+ENC_STATS_MARGIN = 4.0
+
+
+def stats_slot_ids(kind, tile_rows, ho, wo, device="cpu"):
+    """The slot (within its image) of every output pixel, row-major [ho * wo] int64, and the slots per image.
+    kind "halo" / "stem": tiles of tile_rows x 16, slot 4 * tile + wave, wave = tile_rows / 4 rows of the tile;
+    "gemm": 64-pixel tiles of the flat image, slot 2 * tile + half."""
+    pix = torch.arange(ho * wo, device=device)
+    if kind == "gemm":
+        return 2 * (pix // 64) + (pix % 64) // 32, 2 * (-(-(ho * wo) // 64))
+    assert kind in ("halo", "stem") and tile_rows in (8, 16)
+    y, x = pix // wo, pix % wo
+    txn = -(-wo // 16)
+    ids = 4 * ((y // tile_rows) * txn + x // 16) + (y % tile_rows) // (tile_rows // 4)
+    return ids, 4 * txn * (-(-ho // tile_rows))
+
+
+def slot_partials(y, ids, slots, dtype=torch.float64):
+    """(count, mean, M2), each [B, slots, N] in `dtype`, of y [B, HW, N] over the pixels of each slot (ids [HW]);
+    a slot without a pixel is (0, 0, 0).  dtype float32 is the documented per-wave algorithm: an fp32 sum, the
+    mean = sum / count, M2 = the fp32 sum of squared fp32 deviations from that mean."""
+    b, hw, n = y.shape
+    y = y.to(dtype)
+    cnt = torch.zeros(slots, dtype=dtype, device=y.device).index_add_(0, ids, torch.ones(hw, dtype=dtype, device=y.device))
+    s = torch.zeros(b, slots, n, dtype=dtype, device=y.device).index_add_(1, ids, y)
+    c3 = cnt[None, :, None]
+    mean = torch.where(c3 > 0, s / c3.clamp_min(1), torch.zeros_like(s))
+    d = y - mean[:, ids]
+    m2 = torch.zeros_like(s).index_add_(1, ids, d * d)
+    return c3.expand(b, slots, n).contiguous(), mean, m2
+
+
+def chan_merge(cnt, mean, m2):
+    """Chan's merge of partials [B, S, N] over S in slot order, in fp64 -> (n, mean, M2), each [B, N]."""
+    cnt, mean, m2 = cnt.double(), mean.double(), m2.double()
+    n, mu, q = cnt[:, 0].clone(), mean[:, 0].clone(), m2[:, 0].clone()
+    for s in range(1, cnt.shape[1]):
+        nb, mb, qb = cnt[:, s], mean[:, s], m2[:, s]
+        nn = n + nb
+        f = torch.where(nn > 0, nb / nn.clamp_min(1), torch.zeros_like(nn))
+        d = mb - mu
+        mu = mu + d * f
+        q = q + qb + d * d * n * f
+        n = nn
+    return n, mu, q
+
+
+def pooled_stats(cnt, mean, m2):
+    """The pooled (n, mean, M2) of partials [B, S, N] by definition, in fp64: n = sum c, mean = sum c m / n,
+    M2 = sum M2_i + c_i (m_i - mean)^2 (a zero-count slot adds nothing)."""
+    cnt, mean, m2 = cnt.double(), mean.double(), m2.double()
+    n = cnt.sum(1)
+    mu = (cnt * mean).sum(1) / n
+    q = (m2 + cnt * (mean - mu[:, None]) ** 2).sum(1)
+    return n, mu, q
+
+
+def mean_rstd(n, mean, m2, eps=STATS_EPS):
+    """{mean, 1 / sqrt(M2 / n + eps)} with eps the float32 the library receives."""
+    eps = float(np.float32(eps))
+    return mean, 1.0 / torch.sqrt(m2 / n + eps)
+
+
+def instnorm_stats_fp64(y, eps=STATS_EPS):
+    """nn.InstanceNorm2d's statistics of y [B, HW, N] in fp64: (mean, rstd), each [B, N] (biased variance)."""
+    y = y.double()
+    mean = y.mean(1)
+    var = ((y - mean[:, None]) ** 2).mean(1)
+    return mean, 1.0 / torch.sqrt(var + float(np.float32(eps)))
+
+
+def instnorm_stats_restated(y32, ids, slots, eps=STATS_EPS):
+    """The documented algorithm on the float32 output y32 [B, HW, N]: float32 slot partials, Chan's merge in fp64,
+    the result rounded to float32 as the library stores it.  Returns (mean, rstd) float32 [B, N]."""
+    assert y32.dtype == torch.float32
+    mean, rstd = mean_rstd(*chan_merge(*slot_partials(y32, ids, slots, torch.float32)), eps)
+    return mean.float(), rstd.float()
+
+
+def stats_errors(mean, rstd, y):
+    """The errors of merged statistics [B, N] against fp64 over y [B, HW, N]: (the mean's, relative to max |v| of
+    the channel in its image; rstd's, relative), each [B, N] fp64."""
+    m64, r64 = instnorm_stats_fp64(y)
+    vmax = y.double().abs().amax(1).clamp_min(1e-30)
+    return (mean.double() - m64).abs() / vmax, (rstd.double() - r64).abs() / r64
+
+
+def enc_stats_bounds():
+    return ENC_STATS_MARGIN * ENC_STATS_MEASURED["mean"], ENC_STATS_MARGIN * ENC_STATS_MEASURED["rstd"]
+
+
+def stats_mismatch(mean, rstd, ref_mean, ref_rstd, vmax):
+    """The merged-statistics comparison of the GPU tests against reference statistics [B, N] (vmax [B, N]: max |v|
+    of the channel in its image) at enc_stats_bounds().  Returns (entries over a bound, the largest mean error
+    relative to vmax, the largest relative rstd error)."""
+    bm, br = enc_stats_bounds()
+    em = (mean.double() - ref_mean.double()).abs() / vmax.double().clamp_min(1e-30)
+    er = (rstd.double() - ref_rstd.double()).abs() / ref_rstd.double()
+    bad = ~(em <= bm) | ~(er <= br)
+    return int(bad.sum()), float(em.max()), float(er.max())
+
+
+def partials_mismatch(got, ref, y, report=None, blocks=1):
+    """The slot-by-slot comparison of the GPU tests.  got: the kernel's (count, mean, M2) [B, S, N]; ref: the fp64
+    partials of the kernel's own output y [B, HW, N] over the documented footprints.  Returns the number of
+    entries that violate: count exactly equal; |mean - ref| <= dm = 64 u max|v| (a float32 sum of <= 64 terms and
+    one division; max |v| of the channel in its image); |M2 - ref| <= 80 u M2_ref + 2 c dm^2 (a float32 sum of
+    c <= 64 squares of rounded differences, taken about a mean m' that is itself up to dm off: sum (v - m')^2 =
+    M2 + c (m' - m)^2, no first-order term).  blocks = 2 (the halo kernel's 16-row tiles: a slot is two 32-pixel
+    blocks combined by Chan's formula in float32, M2 = M2_a + M2_b + d^2 a b / c with d the difference of the two
+    block means) adds the first-order term of d's error: 2 |d| dm a b / c <= (max v - min v) dm c / 2."""
+    (gc, gm, gq), (rc, rm, rq) = got, ref
+    vmax = y.double().abs().amax(1)[:, None, :]
+    dm = 64 * U * vmax
+    bad = (gc.double() != rc.double())
+    bad |= ~((gm.double() - rm.double()).abs() <= dm)
+    bq = 80 * U * rq.double() + 2 * rc.double() * dm * dm
+    if blocks == 2:
+        bq = bq + (y.double().amax(1) - y.double().amin(1))[:, None, :] * dm * rc.double() / 2
+    bad |= ~((gq.double() - rq.double()).abs() <= bq)
+    if report is not None:
+        for b, s, n in bad.nonzero()[:8].tolist():
+            report.append(f"(image {b}, slot {s}, n {n}): count {float(gc[b, s, n])} / {float(rc[b, s, n])}, mean "
+                          f"{float(gm[b, s, n])!r} / {float(rm[b, s, n])!r}, M2 {float(gq[b, s, n])!r} / "
+                          f"{float(rq[b, s, n])!r}, max|v| {float(vmax[b, 0, n])!r}")
+    return int(bad.sum())
+
+
+def enc_conv_ref(x, w, b, stride, pad, stats=None, relu=True, mutate=None):
+    """conv2d(act(instance_norm(x))) in fp64 with the {mean, rstd} given (stats [B, cin, 2]; None: the plain conv),
+    zero padding staying zero.  x [B, cin, H, W].  mutate (to show that a comparison rejects it): "no_relu",
+    "next_image" (image b reads the statistics of image b - 1), "pad_normalised" (the zero padding normalised like
+    a pixel)."""
+    x, w = x.double(), w.double()
+    b = None if b is None else b.double()
+    if stats is None:
+        return F.conv2d(x, w, b, stride, pad)
+    st = stats.double()
+    if mutate == "next_image":
+        st = torch.roll(st, 1, 0)
+    mean, rstd = st[:, :, 0, None, None], st[:, :, 1, None, None]
+    if mutate == "pad_normalised":
+        x, pad = F.pad(x, (pad[1], pad[1], pad[0], pad[0])), (0, 0)
+    xn = (x - mean) * rstd
+    if relu and mutate != "no_relu":
+        xn = torch.relu(xn)
+    return F.conv2d(xn, w, b, stride, pad)
+
+
+def conv_mismatch(got, ref, tol):
+    """Per image: max |got - ref| against tol x max(1, max |ref|) of that image ([B, ...] tensors).  Returns
+    (the number of images over the bound, the largest error / bound)."""
+    bsz = ref.shape[0]
+    err = (got.double() - ref.double()).abs().reshape(bsz, -1).amax(1)
+    bound = tol * ref.double().abs().reshape(bsz, -1).amax(1).clamp_min(1.0)
+    return int((~(err < bound)).sum()), float((err / bound).max())
