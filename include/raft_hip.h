@@ -198,6 +198,21 @@ int raft_lookup_conv_pack_weight(const void* split_weight, int n_pad, int k_pad,
  * written (no pre-zeroing needed), divided by `scale_div` (1.0f = the
  * reference's unscaled output; sqrtf(C) = AlternateCorrBlock's / sqrt(dim),
  * core/corr.py:198).
+ *
+ * Coordinates, on every entry and kernel form below (tests/test_gpu_alt_corr_forms.py):
+ *   - the sample position is coords / coord_div in fp32; its window is the (2r+2)^2 integer taps
+ *     from floor(position) - r, blended with the fp32 fractions position - floor(position);
+ *   - a finite coordinate, however large: taps off fmap2 are 0, a window wholly off the map gives
+ *     bins of exactly +-0;
+ *   - a non-finite coordinate on either axis (after the division): every bin of that query at
+ *     that level is NaN.  No address depends on such a coordinate.  Queries in other 8x8 query
+ *     tiles are bit-identical to a call in which that query has an ordinary coordinate; queries
+ *     of the same tile stay within the precision's bound (their tile is computed per pixel, in
+ *     exact fp32);
+ *   - flow_out (where an entry has it) is coords - coords_grid in fp32 from the coordinate as
+ *     given, for any coord_div > 0 (inf and NaN follow fp32 arithmetic);
+ *   - backward: a query with a non-finite coordinate, or with |coordinate| >= 1e8 on either
+ *     axis, contributes nothing: no fmap1_grad / fmap2_grad contribution, coords_grad (0, 0).
  * --------------------------------------------------------------------------- */
 int raft_alt_corr_forward(const float* fmap1, const float* fmap2, const float* coords, float* corr,
                           int B, int H1, int W1, int H2, int W2, int C, int N, int radius, float scale_div,
@@ -207,7 +222,14 @@ int raft_alt_corr_forward(const float* fmap1, const float* fmap2, const float* c
  * it); any other value = the fp32-accurate f16x3 box GEMM on MFMA where it applies (r = 4,
  * C % 32 == 0, C <= 256; exact only while |fmap| < 65504: the RAFT forward's range guard covers
  * it), exact fp32 elsewhere.  raft_alt_corr_lookup_nhwc / raft_alt_corr_lookup_levels below
- * are the _prec forms with RAFT_PREC_F16X3. */
+ * are the _prec forms with RAFT_PREC_F16X3.
+ * The box GEMM splits x into hi = f16(x) and an UNSCALED lo = f16(x - hi) and keeps hi*hi +
+ * lo*hi + hi*lo: ~2^-22 of sum_c |f1_c f2_c| per tap while lo is a normal f16, i.e. for feature
+ * values of 2^-3 <= |x| < 65504.  Below 2^-3, lo falls into the f16 subnormals (absolute step
+ * 2^-24), so an element x carries an absolute error of up to 2^-25 whatever its size: maps of
+ * typical magnitude s < 1 lose about a factor 1 / s (measured against fp64 on unit-variance
+ * maps scaled by s, in 2^-24 sum|f1 f2|: 1.2 at s = 1 and 64, 4.4 at 2^-4, 69 at 2^-8; DESIGN.md
+ * 7.3).  RAFT_PREC_FP32 has no such range. */
 int raft_alt_corr_forward_prec(const float* fmap1, const float* fmap2, const float* coords, float* corr,
                                int B, int H1, int W1, int H2, int W2, int C, int N, int radius, float scale_div,
                                int precision, raft_stream_t stream);
@@ -248,7 +270,8 @@ int raft_alt_corr_lookup_levels_prec(const float* fmap1, const float* const* fma
  * of the reference's float atomics; coords_grad is the true gradient through the bilinear
  * weights (the reference leaves it zero, correlation_kernel.cu:307).  workspace: at least
  * raft_alt_corr_backward_workspace_floats(...) floats, 256-byte aligned.  C % 4 == 0,
- * C <= 1024, radius <= 32 (the forward's range). */
+ * C <= 1024, radius <= 32 (the forward's range).  Absent queries (non-finite or |coordinate| >=
+ * 1e8): see "Coordinates" above. */
 int raft_alt_corr_backward(const float* fmap1, const float* fmap2, const float* coords, const float* corr_grad,
                            float* fmap1_grad, float* fmap2_grad, float* coords_grad,
                            int B, int H1, int W1, int H2, int W2, int C, int N, int radius,

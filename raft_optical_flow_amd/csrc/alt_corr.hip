@@ -111,12 +111,16 @@ __device__ __forceinline__ void alt_pixel(const AltArgs& a, long gid, bool valid
       x = a.coords[((long)b * 2) * P1 + p];
       y = a.coords[((long)b * 2 + 1) * P1 + p];
     }
-    x = x / a.coord_div;
-    y = y / a.coord_div;
   }
+  const float xc = x, yc = y;  // the coordinate as given: flow_out = coords - grid
+  x = x / a.coord_div;
+  y = y / a.coord_div;
   const float fx = floorf(x), fy = floorf(y);
   const float dx = x - fx, dy = y - fy;
-  const int x0 = (int)fx - a.r, y0 = (int)fy - a.r;
+  // the origin of a huge coordinate is clamped to +-2^30 (a defined conversion, and x0 + ix cannot
+  // overflow): such a window lies off every map either way; NaN gives a finite origin and NaN weights
+  const int x0 = (int)__builtin_amdgcn_fmed3f(fx, -1073741824.0f, 1073741824.0f) - a.r;
+  const int y0 = (int)__builtin_amdgcn_fmed3f(fy, -1073741824.0f, 1073741824.0f) - a.r;
 
   f32x4 f1[NV];
   const float* f1row = a.f1 + ((long)b * P1 + p) * a.C;
@@ -137,8 +141,9 @@ __device__ __forceinline__ void alt_pixel(const AltArgs& a, long gid, bool valid
   auto tap_in = [&](int t, int& row_off) {
     const int iy = t / wd, ix = t - iy * wd;
     const int h2 = sy0 + iy, w2 = sx0 + ix;
-    row_off = (h2 * a.W2 + w2) * a.C;
-    return valid && t < ntaps && (unsigned)h2 < (unsigned)a.H2 && (unsigned)w2 < (unsigned)a.W2;
+    const bool in = valid && t < ntaps && (unsigned)h2 < (unsigned)a.H2 && (unsigned)w2 < (unsigned)a.W2;
+    row_off = in ? (h2 * a.W2 + w2) * a.C : 0;
+    return in;
   };
   for (int g = 0; g < ntaps; g += 64) {
     f32x4 buf[ALT_PF ? 2 : 1][TB][NV];
@@ -202,7 +207,7 @@ __device__ __forceinline__ void alt_pixel(const AltArgs& a, long gid, bool valid
   }
   if (a.flow && lane < 2) {
     const float gx = lane == 0 ? (float)(p % a.W1) : (float)(p / a.W1);
-    a.flow[((long)b * P1 + p) * a.flow_ld + lane] = (lane == 0 ? x : y) * a.coord_div - gx;
+    a.flow[((long)b * P1 + p) * a.flow_ld + lane] = (lane == 0 ? xc : yc) - gx;
   }
 }
 
@@ -295,9 +300,10 @@ __global__ __launch_bounds__(256) void alt_corr_tile_kernel(AltArgs a) {
       x = a.coords[((long)b * 2) * P1 + p];
       y = a.coords[((long)b * 2 + 1) * P1 + p];
     }
-    x = x / a.coord_div;
-    y = y / a.coord_div;
   }
+  const float xc = x, yc = y;  // the coordinate as given: flow_out = coords - grid
+  x = x / a.coord_div;
+  y = y / a.coord_div;
   const bool fin = isfinite(x) && isfinite(y) && fabsf(x) < 1e8f && fabsf(y) < 1e8f;
   const int x0 = fin ? (int)floorf(x) - R : 0, y0 = fin ? (int)floorf(y) - R : 0;
   // the tile's window box (every wave computes the same one)
@@ -404,8 +410,8 @@ __global__ __launch_bounds__(256) void alt_corr_tile_kernel(AltArgs a) {
     for (int o = g; o < RD * RD; o += 4) alt_bin_store(a, bn, p, x, y, ts, o);
   }
   if (a.flow && g == 0) {
-    a.flow[((long)b * P1 + p) * a.flow_ld + 0] = x * a.coord_div - (float)(p % a.W1);
-    a.flow[((long)b * P1 + p) * a.flow_ld + 1] = y * a.coord_div - (float)(p / a.W1);
+    a.flow[((long)b * P1 + p) * a.flow_ld + 0] = xc - (float)(p % a.W1);
+    a.flow[((long)b * P1 + p) * a.flow_ld + 1] = yc - (float)(p / a.W1);
   }
 }
 
@@ -832,8 +838,8 @@ __global__ __launch_bounds__(512) void alt_corr_mfma_kernel(AltArgs a0, AltLevel
     ALT_ST(12);  // next level setup + first band issue
     if (a0.range_flag && big) *a0.range_flag = 1;
     if (valid && l == 0 && a0.flow && g == 0) {
-      a0.flow[((long)b * P1 + p) * a0.flow_ld + 0] = cur.x * cdiv - (float)(p % a0.W1);
-      a0.flow[((long)b * P1 + p) * a0.flow_ld + 1] = cur.y * cdiv - (float)(p / a0.W1);
+      a0.flow[((long)b * P1 + p) * a0.flow_ld + 0] = xr - (float)(p % a0.W1);  // coords - grid
+      a0.flow[((long)b * P1 + p) * a0.flow_ld + 1] = yr - (float)(p / a0.W1);
     }
     __syncthreads();  // the tap sums are read: the band region takes the next level
     ALT_ST(14);  // flags, flow, final sync
@@ -872,8 +878,11 @@ __global__ __launch_bounds__(256) void alt_corr_generic_kernel(AltArgs a, int ro
     x = a.coords[((long)b * 2) * P1 + p];
     y = a.coords[((long)b * 2 + 1) * P1 + p];
   }
+  const float xc = x, yc = y;  // the coordinate as given: flow_out = coords - grid
   x = x / a.coord_div;
   y = y / a.coord_div;
+  // !fin: no address depends on the coordinate and every tap is off the map (a finite |x| >= 1e8
+  // gives bins of 0, a non-finite one NaN through the weights below)
   const bool fin = isfinite(x) && isfinite(y) && fabsf(x) < 1e8f && fabsf(y) < 1e8f;
   const int x0 = fin ? (int)floorf(x) - a.r : 0, y0 = fin ? (int)floorf(y) - a.r : 0;
   const float* f1row = a.f1 + ((long)b * P1 + p) * a.C;
@@ -881,7 +890,7 @@ __global__ __launch_bounds__(256) void alt_corr_generic_kernel(AltArgs a, int ro
   for (int t = 0; t < wd * wd; ++t) {
     const int h2 = y0 + t / wd, w2 = x0 + t % wd;
     float v = 0.f;
-    if ((unsigned)h2 < (unsigned)a.H2 && (unsigned)w2 < (unsigned)a.W2) {
+    if (fin && (unsigned)h2 < (unsigned)a.H2 && (unsigned)w2 < (unsigned)a.W2) {
       const float* r2 = f2b + ((long)h2 * a.W2 + w2) * a.C;
       for (int c = 4 * lane; c < a.C; c += 256) {
         const f32x4 u = *reinterpret_cast<const f32x4*>(r2 + c);
@@ -912,7 +921,7 @@ __global__ __launch_bounds__(256) void alt_corr_generic_kernel(AltArgs a, int ro
   }
   if (a.flow && lane < 2) {
     const float gx = lane == 0 ? (float)(p % a.W1) : (float)(p / a.W1);
-    a.flow[((long)b * P1 + p) * a.flow_ld + lane] = (lane == 0 ? x : y) * a.coord_div - gx;
+    a.flow[((long)b * P1 + p) * a.flow_ld + lane] = (lane == 0 ? xc : yc) - gx;
   }
 }
 

@@ -121,9 +121,9 @@ __global__ __launch_bounds__(256) void alt_bwd_query_kernel(BwdArgs a) {
     }
     gx = wave_sum(gx);
     gy = wave_sum(gy);
-    if (lane == 0) {
-      a.crg[2 * q] = gx;
-      a.crg[2 * q + 1] = gy;
+    if (lane == 0) {  // an absent query (!fin) has no gradient: exactly 0, not 0 * NaN
+      a.crg[2 * q] = fin ? gx : 0.f;
+      a.crg[2 * q + 1] = fin ? gy : 0.f;
     }
     // fmap1 gradient: sum_t g_t fmap2[tap t]
     for (int t = 0; t < ntaps; ++t) {
