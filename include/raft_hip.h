@@ -88,7 +88,33 @@ int raft_debug_fill_lds_nan(raft_stream_t stream);
  *   off_l = B*H*W * sum_{j<l} S_j.  (64-B tiles = the HBM read granule: a
  *   radius-4 window touches ~10.6 tiles instead of ten straddling row runs.)
  * Level 0 = <fmap1[p], fmap2[q]> / sqrt_c (a division, as core/corr.py:127);
- * level l+1 = 2x2 average pool (floor) of level l.  16-byte aligned buffers.
+ * level l+1 = 2x2 average pool (floor) of level l, bit for bit (((a0+a1)+a2)+a3)/4 of
+ * the stored level l in fp32.  16-byte aligned buffers.
+ *
+ * What the builds read and write (every line asserted by tests/test_gpu_corr_build_forms.py):
+ *   * Only channels 0..C-1 of rows 0..B*H*W-1 are read: the ld - C columns and the memory
+ *     around the operands are never touched.
+ *   * Every float of the pyramid is written.  The padding of every level is exactly 0 in
+ *     the maps of every query whose own features are finite, whatever fmap2 holds; a query
+ *     with a non-finite feature gets non-finite valid elements and unspecified padding at
+ *     level 0 (deeper levels: padding 0).
+ *   * Non-finite features: a NaN or +-Inf in fmap1 row p changes only query p's maps; in
+ *     fmap2 row q of image b it makes non-finite exactly the level-0 element q of every
+ *     query of image b and the pooled cells that contain it (a last row / column that the
+ *     floor pool drops reaches no deeper level).  Every other float of the buffer is bit
+ *     for bit what it is with that feature set to 0.
+ *   * RAFT_PREC_F16X3 magnitude contract.  The split hi = f16(x), lo = f16(x - hi) is
+ *     unscaled.  "~2^-22 relative per product" holds while lo is a normal f16, i.e. for
+ *     features of size 2^-3 .. 2^15: against mag = sum_c |f1_c f2_c| / sqrt_c the largest
+ *     error of the documented arithmetic in fp32 is 1.3 x 2^-24 mag (C = 256; 2.2 at
+ *     C = 64) for N(0, s^2) features at every s from 2^12 down to 2^-2.  Below, lo falls
+ *     into the f16 subnormals (step 2^-24) and the error grows as 1 / s: 1.7 x 2^-24 mag
+ *     at s = 2^-3, 2.8 at 2^-4, 11 at 2^-6, 45 at 2^-8, 730 at 2^-12 (C = 256; C = 64:
+ *     3.4, 6.4, 25, 108, 1380).  RAFT_PREC_FP32 has no such range (3.7 / 4.3 at every s).
+ *   * RAFT_PREC_F16X3 needs |fmap| < 65520 (every value that rounds to a finite f16,
+ *     the largest being 65504).  A larger finite value splits into hi = inf, lo = -inf:
+ *     every element it enters is NaN, exactly as for a non-finite feature (rule above).
+ *     RAFT_PREC_FP32 takes any finite fp32.
  * --------------------------------------------------------------------------- */
 size_t raft_corr_pyramid_floats(int B, int H, int W, int num_levels);
 int raft_corr_build(const float* fmap1, const float* fmap2, int ld, int B, int H, int W, int C,

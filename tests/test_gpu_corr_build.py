@@ -1,6 +1,9 @@
-"""GPU checks of the f16x3 correlation build (raft_corr_build_prec: corr_build2_kernel; CorrBlock.__init__ /
-CorrBlock.corr, core/corr.py:25-54,96-127) beyond the oracle parity of test_gpu_parity.py: the work-group
--> tile order is a pure permutation, so every order gives the same pyramid bit for bit."""
+"""GPU checks of the f16x3 correlation builds (CorrBlock.__init__ / CorrBlock.corr, core/corr.py:25-54,96-127)
+beyond the oracle parity of test_gpu_parity.py.  raft_corr_build_prec (corr_build2_kernel, 128 x 128 tiles): the
+work-group -> tile order is a pure permutation, so every order gives the same pyramid bit for bit.
+raft_corr_build_ws (corr_split4_kernel + corr_build4_kernel, 256 x 256 units, the forward's build): max-norm
+parity with fp64 at four shapes, exact pooling of levels 1 and 2, the 4-wave form, the fallbacks and the workspace
+rule.  The element-by-element comparison of every build form with fp64 is tests/test_gpu_corr_build_forms.py."""
 import pytest
 import torch
 
