@@ -82,16 +82,9 @@ __device__ __forceinline__ float transpose_reduce(float (&v)[N], int lane) {
 }
 
 // waves per SIMD the forward kernel is compiled for at C <= 256 (8 / NV above; register budget: its tap
-// group's loads all in flight vs more waves); dev builds may override it
-#ifndef ALT_WAVES
-#define ALT_WAVES 8
-#endif
-#ifndef ALT_PF  // 1: the next batch's loads go out before this batch's products
-#define ALT_PF 1
-#endif
-#ifndef ALT_TB  // taps per load batch
-#define ALT_TB 2
-#endif
+// group's loads all in flight vs more waves)
+constexpr int ALT_WAVES = 8;
+constexpr int ALT_TB = 2;  // taps per load batch
 // One query pixel gid = (b*N + n)*P1 + p by one wave (ts: the wave's 128-float
 // LDS row of tap sums).
 template <int NV>
@@ -146,7 +139,7 @@ __device__ __forceinline__ void alt_pixel(const AltArgs& a, long gid, bool valid
     return in;
   };
   for (int g = 0; g < ntaps; g += 64) {
-    f32x4 buf[ALT_PF ? 2 : 1][TB][NV];
+    f32x4 buf[2][TB][NV];
 #pragma unroll
     for (int j = 0; j < TB; ++j) {
       int ro;
@@ -156,21 +149,13 @@ __device__ __forceinline__ void alt_pixel(const AltArgs& a, long gid, bool valid
 #pragma unroll
     for (int jb = 0; jb < 64; jb += TB) {
       if (g + jb >= ntaps) break;  // wave-uniform
-      const int cur = ALT_PF ? (jb / TB) & 1 : 0;
-      if (!ALT_PF && jb > 0) {
-#pragma unroll
-        for (int j = 0; j < TB; ++j) {
-          int ro;
-          const bool in = tap_in(g + jb + j, ro);
-          tap_load<NV>(buf[0][j], rs, in, ro, lane, a.C);
-        }
-      }
-      if (ALT_PF && jb + TB < 64) {
+      const int cur = (jb / TB) & 1;
+      if (jb + TB < 64) {
 #pragma unroll
         for (int j = 0; j < TB; ++j) {
           int ro;
           const bool in = tap_in(g + jb + TB + j, ro);
-          tap_load<NV>(buf[ALT_PF ? cur ^ 1 : 0][j], rs, in, ro, lane, a.C);
+          tap_load<NV>(buf[cur ^ 1][j], rs, in, ro, lane, a.C);
         }
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -239,12 +224,8 @@ __global__ __launch_bounds__(256, NV == 1 ? ALT_WAVES : 8 / NV) void alt_corr_ke
 // alt_corr_kernel.
 // ============================================================================
 constexpr int AT = 8;     // tile side (query pixels)
-#ifndef ALT_ACC  // (dev builds may override the chunk and box sizes)
-#define ALT_ACC 8
-#endif
-#ifndef ALT_ATB
-#define ALT_ATB 28
-#endif
+constexpr int ALT_ACC = 8;
+constexpr int ALT_ATB = 28;
 constexpr int ACC = ALT_ACC;  // channels per staged chunk
 constexpr int ATB = ALT_ATB;  // max bounding-box side (fmap2 pixels)
 
@@ -423,17 +404,15 @@ __global__ __launch_bounds__(256) void alt_corr_tile_kernel(AltArgs a) {
 // queries, N = box pixels, K = C) of which each query keeps its (2r+2)^2 window
 // entries.  The VALU tile kernel reads LDS once per (query, tap, 8 channels);
 // here the box (up to 96 x 96 fmap2 pixels, where the VALU kernel stops at 28 x 28)
-// is consumed in bands of whole box rows (96 / box width of them, N padded to 96) on v_mfma_f32_32x32x16_f16 in the fp32-accurate split (hi*hi + lo*hi +
-// hi*lo, the corr_build arithmetic), and the band's 64 x 64 product goes through
+// is consumed in bands of whole box rows (96 / box width of them, N padded to 96) on
+// v_mfma_f32_16x16x32_f16 in the fp32-accurate split (hi*hi + lo*hi +
+// hi*lo, the corr_build arithmetic), and the band's 64 x 96 product goes through
 // LDS where every query picks the taps of its window that lie in the band.
 //   LDS: F1 tile, all K, split (64 x C/32 x 128 B = 64 KB) | band rows of F2
 //   (96 px x C/32 x 128 B, reused for the band's S) -> 160 KB, one work-group
-//   per CU; 8 waves load, waves 0-5 own one 32x32 S subtile each, all 8 pick taps.
+//   per CU; 8 waves load, own one 16x48 S block each and pick taps.
 // The next band's fmap2 loads are issued before the current band's MFMAs.
 // ============================================================================
-#ifndef ALT_MFMA16
-#define ALT_MFMA16 1  // the box GEMM on 16x16 blocks: 1 = 8 waves, 2 = 4 waves of 32 rows (0: 6 waves of 32x32 blocks)
-#endif
 constexpr int AM_KS = 8;                 // 32-channel K-steps (C <= 256)
 constexpr int AM_ROW = 128;              // bytes per (row, K-step): 32 hi | 32 lo halves, 16-B chunks
                                          // XOR-swizzled by row & 7 (conflict-free fragment reads)
@@ -556,10 +535,6 @@ __global__ __launch_bounds__(512) void alt_corr_mfma_kernel(AltArgs a0, AltLevel
     }
   }
   ALT_ST(0);  // F1 tile
-#if !ALT_MFMA16
-  const int mi = g & 1, ni = g >> 1;  // S subtile of MFMA waves 0-5
-  const int m = lane & 31, h = lane >> 5;
-#endif
   // ---- per-level window box (wave-uniform) and the band loads, set up one level ahead ------
   struct Lvl {
     float x, y;       // this lane's query at the level
@@ -620,14 +595,7 @@ __global__ __launch_bounds__(512) void alt_corr_mfma_kernel(AltArgs a0, AltLevel
 #pragma unroll
     for (int k = 0; k < AM_PER; ++k) {
       const int j = g + 8 * k, s = lane >> 3;
-#ifdef ALT_ABL_NOSPLIT  // dev ablation (wrong results): the band stored as loaded, one 16-B write per load
-      if (s < ks) {
-        const int row = s * AM_NB + j;
-        *reinterpret_cast<f32x4*>(Bs + row * AM_ROW + am_chunk(row, lane & 7)) = bv[k];
-      }
-#else
       if (s < ks) am_split_store(Bs, s * AM_NB + j, lane & 7, bv[k]);
-#endif
     }
   };
   Lvl cur;
@@ -676,85 +644,43 @@ __global__ __launch_bounds__(512) void alt_corr_mfma_kernel(AltArgs a0, AltLevel
       ALT_ST(3);
       if (r0 + cur.br < cur.bh) load_band(l, cur, r0 + cur.br);  // in flight under the MFMAs
       ALT_ST(4);
-#if ALT_MFMA16
-      // the band product on 16x16 blocks, every SIMD the same share.  ALT_MFMA16 == 1: all 8 waves,
-      // wave g owns query rows 16 (g & 3) .. +15 x band pixels 48 (g >> 2) .. +47 (RB = 1 row block
-      // of 3 column blocks); == 2: waves 0-3 (one per SIMD), wave g query rows 32 (g & 1) .. +31 x
-      // band pixels 48 (g >> 1) .. +47 (RB = 2): the same MFMA cycles per SIMD from 37 % fewer LDS
-      // fragment bytes (the 32x32 form ran on waves 0-5: SIMDs 0 and 1 carried two waves' MFMAs)
-      constexpr int RB = ALT_MFMA16 == 2 ? 2 : 1;
-      f32x4 c0[RB][3] = {}, c1[RB][3] = {}, c2[RB][3] = {};
-      const int rb = RB == 2 ? (g & 1) : (g & 3), cg = RB == 2 ? (g >> 1) : (g >> 2);
+      // the band product on 16x16 blocks, every SIMD the same share: wave g owns query rows
+      // 16 (g & 3) .. +15 x band pixels 48 (g >> 2) .. +47, one row block of 3 column blocks (the forms on
+      // 32-row blocks and on 32x32 blocks of waves 0-5: profiles/r05n_experiments.txt, r05l_experiments.txt)
+      f32x4 c0[3] = {}, c1[3] = {}, c2[3] = {};
+      const int rb = g & 3, cg = g >> 2;
       const int rl = lane & 15, kg = lane >> 4;
-      if (RB == 1 || g < 4) {
-        for (int s = 0; s < ks; ++s) {
-          h8 xh[RB], xl[RB];
+      for (int s = 0; s < ks; ++s) {
+        h8 xh, xl;
+        // (a loop of one trip, left from the forms with two row blocks per wave: without it the compiler
+        // allocates two register pairs of this kernel the other way round)
 #pragma unroll
-          for (int i = 0; i < RB; ++i) {
-            const int ar = s * (AT * AT) + 16 * (RB * rb + i) + rl;
-            const char* Ar = As + ar * AM_ROW;
-            xh[i] = *reinterpret_cast<const h8*>(Ar + am_chunk(ar, kg));
-            xl[i] = *reinterpret_cast<const h8*>(Ar + am_chunk(ar, 4 + kg));
-          }
-#pragma unroll
-          for (int t = 0; t < 3; ++t) {
-            const int brow = s * AM_NB + 48 * cg + 16 * t + rl;
-            const char* Br = Bs + brow * AM_ROW;
-            const h8 yh = *reinterpret_cast<const h8*>(Br + am_chunk(brow, kg));
-            const h8 yl = *reinterpret_cast<const h8*>(Br + am_chunk(brow, 4 + kg));
-#pragma unroll
-            for (int i = 0; i < RB; ++i) {
-              c0[i][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xh[i], yh, c0[i][t], 0, 0, 0);
-              c1[i][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xl[i], yh, c1[i][t], 0, 0, 0);
-              c2[i][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xh[i], yl, c2[i][t], 0, 0, 0);
-            }
-          }
-        }
-      }
-      ALT_ST(5);  // MFMAs
-      __syncthreads();  // every MFMA wave has read the band: its region takes S
-      ALT_ST(6);
-      // register r of block (i, t) holds S[query 16 (RB rb + i) + 4 kg + r][band pixel 48 cg + 16 t + rl]
-      if (RB == 1 || g < 4) {
-#pragma unroll
-        for (int i = 0; i < RB; ++i)
-#pragma unroll
-          for (int t = 0; t < 3; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-              S[(16 * (RB * rb + i) + 4 * kg + r) * AM_SLD + 48 * cg + 16 * t + rl] =
-                  c0[i][t][r] + c1[i][t][r] + c2[i][t][r];
-      }
-#else
-      f32x16 acc = {}, acc2 = {}, acc3 = {};
-      if (g < 6) {
-        for (int s = 0; s < ks; ++s) {
-          const int ar = s * (AT * AT) + 32 * mi + m, brow = s * AM_NB + 32 * ni + m;
+        for (int i = 0; i < 1; ++i) {
+          const int ar = s * (AT * AT) + 16 * rb + rl;
           const char* Ar = As + ar * AM_ROW;
-          const char* Br = Bs + brow * AM_ROW;
+          xh = *reinterpret_cast<const h8*>(Ar + am_chunk(ar, kg));
+          xl = *reinterpret_cast<const h8*>(Ar + am_chunk(ar, 4 + kg));
+        }
 #pragma unroll
-          for (int qq = 0; qq < 2; ++qq) {
-            const int c = 2 * qq + h;  // the lane's 8 halves of this K-half: logical chunk c (hi), 4 + c (lo)
-            const h8 xh = *reinterpret_cast<const h8*>(Ar + am_chunk(ar, c));
-            const h8 xl = *reinterpret_cast<const h8*>(Ar + am_chunk(ar, 4 + c));
-            const h8 yh = *reinterpret_cast<const h8*>(Br + am_chunk(brow, c));
-            const h8 yl = *reinterpret_cast<const h8*>(Br + am_chunk(brow, 4 + c));
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(xh, yh, acc, 0, 0, 0);
-            acc2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(xl, yh, acc2, 0, 0, 0);
-            acc3 = __builtin_amdgcn_mfma_f32_32x32x16_f16(xh, yl, acc3, 0, 0, 0);
-          }
+        for (int t = 0; t < 3; ++t) {
+          const int brow = s * AM_NB + 48 * cg + 16 * t + rl;
+          const char* Br = Bs + brow * AM_ROW;
+          const h8 yh = *reinterpret_cast<const h8*>(Br + am_chunk(brow, kg));
+          const h8 yl = *reinterpret_cast<const h8*>(Br + am_chunk(brow, 4 + kg));
+          c0[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xh, yh, c0[t], 0, 0, 0);
+          c1[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xl, yh, c1[t], 0, 0, 0);
+          c2[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xh, yl, c2[t], 0, 0, 0);
         }
       }
       ALT_ST(5);  // MFMAs
       __syncthreads();  // every MFMA wave has read the band: its region takes S
       ALT_ST(6);
-      if (g < 6) {
-        // register r holds S[query 32mi + (r&3) + 8(r>>2) + 4h][band pixel 32ni + m]
+      // register r of block t holds S[query 16 rb + 4 kg + r][band pixel 48 cg + 16 t + rl]
 #pragma unroll
-        for (int r = 0; r < 16; ++r)
-          S[(32 * mi + (r & 3) + 8 * (r >> 2) + 4 * h) * AM_SLD + 32 * ni + m] = acc[r] + acc2[r] + acc3[r];
-      }
-#endif
+      for (int t = 0; t < 3; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          S[(16 * rb + 4 * kg + r) * AM_SLD + 48 * cg + 16 * t + rl] = c0[t][r] + c1[t][r] + c2[t][r];
       ALT_ST(7);  // S stores
       __syncthreads();
       ALT_ST(8);
@@ -934,7 +860,6 @@ int launch_alt(const AltArgs& a, raft_stream_t stream) {
                        (size_t)(4 * row * sizeof(float)), s, a, row);
     return check_launch("raft_alt_corr(generic radius)");
   }
-#ifndef ALT_NO_TILE  // dev builds: the per-pixel kernel at every size
   static const bool mfma = [] {
     const char* e = getenv("RAFT_ALT_MFMA");
     return !(e && e[0] == '0');
@@ -956,7 +881,6 @@ int launch_alt(const AltArgs& a, raft_stream_t stream) {
     hipLaunchKernelGGL(alt_corr_tile_kernel<4>, dim3((unsigned)tiles), dim3(256), 0, s, a);
     return check_launch("raft_alt_corr");
   }
-#endif
   const long waves = (long)a.B * a.N * a.H1 * a.W1;
   dim3 grid((unsigned)cdiv_l(waves, 4));
   if (a.C <= 256)

@@ -47,12 +47,7 @@ constexpr int BK = 32;
 constexpr int LDSK = BK + 4;
 constexpr int STAGE = (BM + BN) * LDSK;       // floats per LDS buffer
 constexpr int MAX_GATHER_K = 1024;
-#ifndef CONV_SCHED
-#define CONV_SCHED 1                              // sched_group_barrier interleave of a phase
-#endif
-#ifndef GEMM_NS
-#define GEMM_NS 2                                 // staging register sets (NS-1 K-steps in flight + one refilling)
-#endif            // k_pad limit of GATHER mode (LDS table)
+constexpr int GEMM_NS = 2;                    // staging register sets (NS-1 K-steps in flight + one refilling)
 
 struct ConvArgs {
   raft_conv2d_params p;
@@ -237,14 +232,8 @@ __global__ __launch_bounds__(256 * KG, 4) void conv_gemm_kernel(ConvArgs a) {  /
         const unsigned pix = (unsigned)w.pb[i] + __umul24((unsigned)iy, in_w) + (unsigned)ix;
         voff[i] = ok ? __umul24(pix, ldb) + lq * 16u : OFF_INVALID;
       }
-#ifdef ABL_NOLOAD  // timing ablation (dev builds only): no A/B global loads
-      ra[0] = f32x4{(float)voff[0], 1.f, 2.f, 3.f};
-      ra[1] = f32x4{(float)voff[1], 1.f, 2.f, (float)soff};
-      (void)rs;
-#else
       ra[0] = buf_load4(rs, voff[0], soff);
       ra[1] = buf_load4(rs, voff[1], soff);
-#endif
       am = 0xFFu;
       wcs += KG * BK;
       advance_tap();
@@ -252,15 +241,10 @@ __global__ __launch_bounds__(256 * KG, 4) void conv_gemm_kernel(ConvArgs a) {  /
     } else {
       am = kstep < nk ? gather_a(a, w, kstep, lq, ktab, ra) : 0u;
     }
-#ifdef ABL_NOLOAD
-    rb[0] = f32x4{(float)wsoff, 1.f, 2.f, 3.f};
-    rb[1] = f32x4{(float)wsoff, 1.f, 2.f, 4.f};
-#else
     // past the last K-step the soffset points beyond the weight buffer: zeros
     const unsigned ws = kstep < nk ? wsoff : OFF_INVALID;
     rb[0] = buf_load4(rs_w, wvoff0, ws);
     rb[1] = buf_load4(rs_w, wvoff1, ws);
-#endif
     wsoff += KG * BK * 4u;
     kstep += KG;
   };
@@ -359,7 +343,6 @@ __global__ __launch_bounds__(256 * KG, 4) void conv_gemm_kernel(ConvArgs a) {  /
   // the MFMA pipe is fed while the split runs and the loads queue at the
   // texture unit in the MFMA shadow (not all at once after the barrier)
   auto interleave = [&]() {
-#if CONV_SCHED
     constexpr int NMF = PREC == RAFT_PREC_FP32 ? 16 : PREC == RAFT_PREC_F16X3 ? 6 : 2;
     constexpr int NRD = (PREC == RAFT_PREC_F16 || PREC == RAFT_PREC_BF16) ? 4 : 8;
     constexpr int NVA = PREC == RAFT_PREC_FP32 ? 1 : PREC == RAFT_PREC_F16X3 ? 6 : 10;
@@ -374,20 +357,8 @@ __global__ __launch_bounds__(256 * KG, 4) void conv_gemm_kernel(ConvArgs a) {  /
       if (i < 4) __builtin_amdgcn_sched_group_barrier(0x20, 1, 0);  // the next step's global loads
     }
     __builtin_amdgcn_sched_group_barrier(0x200, 4, 0);
-#endif
   };
 
-#ifdef ABL_EMPTY
-  if (a.M > 0) return;
-#endif
-#ifdef ABL_NOLOOP
-  if (a.M > 0) {
-    int rows[16];
-    for (int r = 0; r < 16; ++r) rows[r] = -1;
-    tile_epilogue(p, rows, n0 + wn * 32 + (lane & 31), acc);
-    return;
-  }
-#endif
   // prologue: K-steps 0 .. NS-1 issued into sets 0 .. NS-1, step 0 staged
 #pragma unroll
   for (int u = 0; u < NS; ++u) issue(ra[u], rb[u], am[u]);
@@ -410,18 +381,14 @@ __global__ __launch_bounds__(256 * KG, 4) void conv_gemm_kernel(ConvArgs a) {  /
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       issue(ra[u % NS], rb[u % NS], am[u % NS]);
-#ifndef ABL_NOCOMPUTE
       compute(u & 1);
-#endif
       stage((u + 1) & 1, ra[(u + 1) % NS], rb[(u + 1) % NS], am[(u + 1) % NS]);
       interleave();
 #ifdef STAMPS
       const unsigned long long st1 = stamp_now();
       st_work += st1 - st0;
 #endif
-#ifndef ABL_NOBARRIER
       __syncthreads();
-#endif
 #ifdef STAMPS
       st0 = stamp_now();
       st_bar += st0 - st1;
@@ -543,11 +510,9 @@ __global__ __launch_bounds__(256) void conv_smalln_kernel(ConvArgs a) {
 // 4 channels; the (TH+2)x18 input patch is staged in LDS as [channel quad][patch
 // pixel] (row stride padded to 109 pixels).  Partial sums meet through lane
 // shuffles (the 8 quads) and LDS (the 8 waves) in a fixed order.
-#ifndef SN_TH4_MIN_TILES  // dev builds: 0 = always 4x16 tiles
-// 256 (one round; 512 until r04k: config 5's 510 4x16 tiles vs 1020 2x16 ones, 47.9 / 48.0 -> 48.3 / 48.4
-// pairs/s on one box); RAFT_SN_TH4_MIN overrides
-#define SN_TH4_MIN_TILES 256
-#endif
+// 4x16 tiles from 256 tiles up (one round; 512 until r04k: config 5's 510 4x16 tiles vs 1020 2x16 ones,
+// 47.9 / 48.0 -> 48.3 / 48.4 pairs/s on one box); RAFT_SN_TH4_MIN overrides
+constexpr int SN_TH4_MIN_TILES = 256;
 // TH x 16 output tiles (TH = 4 or 2); SN_PXB = TH*16/8 pixels per lane block
 template <int TH>
 struct SnGeom {
@@ -580,10 +545,7 @@ __global__ __launch_bounds__(512) void conv_smalln3x3_kernel(ConvArgs a, const f
     for (int j = 0; j < NOUT; ++j) acc[i][j] = 0.f;
   // ADD_TO_OUT (coords1 += delta_flow): the destination value loaded here, with the patch, not after
   // the reduction (one memory round trip fewer on the kernel's path)
-#ifndef SN_PRE
-#define SN_PRE 1
-#endif
-  const bool pre_on = SN_PRE && p.epilogue == RAFT_EPI_ADD_TO_OUT && !p.add0;
+  const bool pre_on = p.epilogue == RAFT_EPI_ADD_TO_OUT && !p.add0;
   const int ej = threadIdx.x >> 6;
   const int ey = y0 + (lane >> 4), ex = x0 + (lane & 15);
   const bool eok = threadIdx.x < 64 * NOUT && ej < p.n && lane < SN_TH * SN_TW && ey < p.out_h && ex < p.out_w;

@@ -110,24 +110,9 @@ struct HaloCfg {
   static constexpr int PH = TH + KH - 1, PW = HTW + KW - 1, NPIX = PH * PW;
   static constexpr int PI = (NPIX + 7) / 8;  // 1-KiB DMA pieces per patch
   // load sets in flight ahead of the super-step: 3, or 2 where 3 does not fit
-#ifdef HALO_D  // dev builds: deeper load rings where they fit
-  static constexpr int D = halo_lds_bytes(T, U, HALO_D, BNT, PI, WR) <= LB   ? HALO_D
-                           : halo_lds_bytes(T, U, 3, BNT, PI, WR) <= LB ? 3
-                                                                              : 2;
-#else
   static constexpr int D = halo_lds_bytes(T, U, 3, BNT, PI, WR) <= LB ? 3 : 2;
-#endif
   static constexpr int PA = patch_slots(T, U, D);
-  // DW: the weight DMAs' lead in super-steps (dev builds: HALO_WX more than the patches' D on the
-  // pre-split patch path where the longer weight ring fits)
-#ifndef HALO_WX
-#define HALO_WX 0
-#endif
-  static constexpr int DW = (T > 1 && D == 3 && HALO_WX > 0 &&
-                             U * (D + HALO_WX + 1) * BNT * WR + PA * PI * 1024 + 16 * 1024 <= LB)
-                                ? D + HALO_WX
-                                : D;
-  static constexpr int SB = U * (DW + 1);  // weight-block ring (K-steps)
+  static constexpr int SB = U * (D + 1);  // weight-block ring (K-steps)
   static constexpr int LDS_B = SB * BNT * WR, LDS_A = PA * PI * 1024;
 };
 
@@ -196,7 +181,6 @@ __device__ __forceinline__ void halo_body(const HaloArgs* args, int prob, int nt
   constexpr bool BF = PREC == RAFT_PREC_BF16;
   using C = HaloCfg<KH, KW, BNT, X3 ? 128 : 64, TH>;
   constexpr int T = C::T, U = C::U, D = C::D, PW = C::PW, NPIX = C::NPIX, PI = C::PI, PA = C::PA, SB = C::SB;
-  constexpr int DW = C::DW;  // weight lead (== D unless HALO_WX)
   // Weight rows in LDS: f16x3 the packed K-step row as it is (32 hi then 32 lo halves, 128 B);
   // the one-product modes (F16, BF16) read only hi, so only the 64-B hi half of each row
   // moves (half the weight bytes a CU ingests per K-step).  16-B quads XOR-swizzled by row
@@ -207,15 +191,7 @@ __device__ __forceinline__ void halo_body(const HaloArgs* args, int prob, int nt
   constexpr int RPP = 1024 / WROW;             // rows per 1-KiB DMA piece
   constexpr int NBI = BNT / RPP;    // 1-KiB DMA pieces per weight block (one K-step)
   constexpr int NWP = U * NBI / NL;  // weight pieces per loader wave per load set
-  // KSW (KS = 2, dev builds -DHALO_KSW=1): the compute waves issue the weight DMAs (NWPC pieces each per load
-  // set) and the loaders stage only the patches.  Measured slower than the loaders issuing both (the DMA issue
-  // sits in the compute waves' MFMA stream: profiles/r06b_experiments.txt), so off by default.
-#ifndef HALO_KSW
-#define HALO_KSW 0
-#endif
-  constexpr bool KSW = KS > 1 && HALO_KSW;
-  constexpr int NWPC = KSW ? U * NBI / (4 * KS) : 1;
-  constexpr int LNWP = KSW ? 0 : NWP;  // weight pieces a loader issues per load set
+  // (KS = 2 with the compute waves issuing the weight DMAs: slower, profiles/r06b_experiments.txt)
   // Compute waves (32-pixel MFMA row blocks = two tile rows): TH = 8, BNT <= 64: 4 waves along M,
   // each one block (tile rows 2w, 2w+1) x all BNT columns; TH = 8, BNT = 128 (the one-product
   // modes' wide tiles): 2 x 2 waves, each 2 blocks (64 pixels) x 64 columns; TH = 16, BNT = 64:
@@ -234,33 +210,23 @@ __device__ __forceinline__ void halo_body(const HaloArgs* args, int prob, int nt
   // pre-split (f16 hi | lo, the weight-row format), so the MFMA waves read
   // ready fragments; 1x1 convs (a patch per K-step, D = 2) keep fp32 patches
   // moved by LDS-DMA and split in the MFMA waves.
-#ifndef HALO_NOLSPLIT  // dev builds: the update convs' patches as fp32 by LDS-DMA, split by the compute waves
-#define HALO_NOLSPLIT 0
-#endif
-  constexpr bool LSPLIT = T > 1 && D == 3 && !(HALO_NOLSPLIT && !ENC);
+  constexpr bool LSPLIT = T > 1 && D == 3;
   // SGB: the pre-split path's fragment reads of K-step j+1 pinned into K-step j's MFMA stream, SGB reads
   // per MFMA gap, one K-step per scheduling region.  Left to itself the compiler sinks each read to just
   // before its MFMA and waits lgkmcnt(1) there (the LDS round trip exposed several times per K-step).
   // One read per gap: the update convs -4 % (tools/conv_bench.py, profiles/r06_experiments.txt); two or
   // more per gap, or the encoders' multi-tile bodies, run out of VGPRs at 768 threads and spill.
-#ifndef HALO_SGB
-#define HALO_SGB 1
-#endif
-  constexpr int SGB = (ENC && NL == 8) ? 0 : HALO_SGB;
+  constexpr int SGB = (ENC && NL == 8) ? 0 : 1;
   // RELAX (with SGB's pinned regions): the barrier at the end of a super-step waits only for the reads of
   // its own load sets, not for the look-ahead reads of the next super-step's first K-step issued in its last
   // K-step (lgkmcnt(NRD) instead of lgkmcnt(0): LDS reads complete in order), so the last read's LDS round
   // trip is not exposed at every barrier.  Safe for the weight ring (the next super-step overwrites the slot
   // of the set just finished) and, where patch_slots(.., late = 1) needs no extra slot, for the patch ring.
-#ifndef HALO_RELAX
-#define HALO_RELAX 1
-#endif
   constexpr int NRD1 = NSUB * 2 * (X3 ? 2 : 1) + MF * 2 * (X3 ? 2 : 1);  // LDS reads per K-step
-  constexpr bool RELAX = HALO_RELAX && SGB > 0 && LSPLIT && !MT && patch_slots(T, U, D, 1) == PA && NRD1 <= 15;
+  constexpr bool RELAX = SGB > 0 && LSPLIT && !MT && patch_slots(T, U, D, 1) == PA && NRD1 <= 15;
   static_assert(D >= 2 && C::LDS_B + C::LDS_A <= C::LB, "LDS budget");
-  static_assert(KS == 1 || (KS == 2 && !MT && !ENC && LSPLIT && SGB > 0 && MF == 1 && NSUB <= 2 && (NL == 4 || NL == 8) &&
-                            SB % 2 == 0 && 8 * 4096 <= C::LDS_B + C::LDS_A && (DW == D || !KSW) && NBI % NWPC == 0 &&
-                            NWPC >= 1),
+  static_assert(KS == 1 || (KS == 2 && !MT && !ENC && LSPLIT && SGB > 0 && MF == 1 && NSUB == 2 && NL == 4 &&
+                            SB % 2 == 0 && 8 * 4096 <= C::LDS_B + C::LDS_A),
                 "the K-split form: one tile of 32 x 64 blocks on the pre-split path, 4 loaders");
   static_assert(NWP >= 1 && NBI % NWP == 0, "a wave's weight pieces lie in one K-step");
   static_assert(U % 2 == 0 && (T == 1 || T >= U), "fragment parity; at most one chunk start per load set");
@@ -339,32 +305,6 @@ __device__ __forceinline__ void halo_body(const HaloArgs* args, int prob, int nt
     return q;
   };
   const WPieces wp0 = wpieces(lw);
-  // the compute waves' pieces (KSW): NWPC consecutive pieces of one K-step's block per compute wave
-  struct WPiecesC {
-    int ew, wpc0;
-    unsigned off[NWPC];
-  };
-  auto wpieces_c = [&](int ci) {
-    WPiecesC q;
-    q.ew = (ci * NWPC) / NBI;
-    q.wpc0 = (ci * NWPC) % NBI;
-#pragma unroll
-    for (int k = 0; k < NWPC; ++k) {
-      const int r = RPP * (q.wpc0 + k) + lane / QPR;
-      const int qd = X3 ? (lane & 7) ^ ((r >> 1) & 7) : (lane & 3) ^ ((r >> 2) & 3);
-      q.off[k] = (unsigned)(r + nt * BNT) * ((unsigned)a.K * 4u) + (unsigned)qd * 16u;
-    }
-    return q;
-  };
-  auto issue_weights_c = [&](int u, const WPiecesC& q) {  // (!MT: load set u of the one tile)
-    const int j = U * u + q.ew;
-    const bool in = j < nk;
-    const int c = j / T, t = j - c * T;
-    const unsigned soff = in ? (unsigned)(t * nch + c) * 128u : 0u;
-    char* dst = smem + (U * (u % (DW + 1)) + q.ew) * (BNT * WROW) + q.wpc0 * 1024;
-#pragma unroll
-    for (int k = 0; k < NWPC; ++k) dma16(rs_w, dst + k * 1024, in ? q.off[k] : OFF_INVALID, soff);
-  };
   auto issue_weights_q = [&](int u, const WPieces& q) {
     int kt, ul;
     set_tile(u, kt, ul);
@@ -374,7 +314,7 @@ __device__ __forceinline__ void halo_body(const HaloArgs* args, int prob, int nt
     const int n0 = MT && in ? nt * BNT : 0;
     // packed K-step (tap, chunk) of the tile's N-tile rows
     const unsigned soff = in ? (unsigned)(t * nch + c) * 128u + (unsigned)n0 * ((unsigned)a.K * 4u) : 0u;
-    char* dst = smem + (U * (u % (DW + 1)) + q.ew) * (BNT * WROW) + q.wpc0 * 1024;
+    char* dst = smem + (U * (u % (D + 1)) + q.ew) * (BNT * WROW) + q.wpc0 * 1024;
 #pragma unroll
     for (int k = 0; k < NWP; ++k) dma16(rs_w, dst + k * 1024, in ? q.off[k] : OFF_INVALID, soff);
   };
@@ -397,9 +337,6 @@ __device__ __forceinline__ void halo_body(const HaloArgs* args, int prob, int nt
   }
 
   if (loader) {
-#ifdef HALO_LPRIO  // dev builds: the loader waves' issue priority
-    __builtin_amdgcn_s_setprio(HALO_LPRIO);
-#endif
     // ---- loader waves ------------------------------------------------------
     // (the weights of the prologue's load sets 0 .. D-1 are issued by the MFMA
     // waves, which have nothing else to do then: an LDS-DMA costs its issuing
@@ -570,39 +507,6 @@ __device__ __forceinline__ void halo_body(const HaloArgs* args, int prob, int nt
           }
         }
       };
-#ifdef HALO_ABL_PDMA
-      // TIMING ABLATION (dev builds only, WRONG results): the patches moved by LDS-DMA as they are in
-      // memory (fp32) into the pre-split slots, no register staging and no split -- the bound on what
-      // pre-split activation rows in memory would give the loaders (the update convs only)
-      if constexpr (!ENC) {
-#pragma unroll
-        for (int u = 0; u < D; ++u) {
-          int kt, c;
-          if (set_chunk(u, kt, c)) issue_patch(kt, c);
-        }
-        wait_vm<0>();
-        __builtin_amdgcn_s_barrier();
-        for (int s = 0; s < NS; ++s) {
-          int nnew = 0;
-          if (s + D < NS) {
-            int kt, c;
-            if (set_chunk(s + D, kt, c)) {
-              issue_patch(kt, c);
-              nnew += pcw;
-            }
-            if constexpr (DW == D) {
-              issue_weights(s + D);
-              nnew += NWP;
-            }
-          }
-          wait_vm_n(s + 1 < NS ? nnew : 0);
-          __builtin_amdgcn_s_barrier();
-        }
-        wait_vm<0>();
-        if constexpr (KS > 1) __builtin_amdgcn_s_barrier();
-        return;
-      }
-#endif
       constexpr int PMAX = (U * D + T - 1) / T + 1;  // chunk starts in the prologue's sets
       Staged pv[PMAX];
       int pks[PMAX], pcs[PMAX];
@@ -640,7 +544,7 @@ __device__ __forceinline__ void halo_body(const HaloArgs* args, int prob, int nt
 #endif
       for (int s = 0; s < NS; ++s) {
         if (pend_k >= 0) {
-          wait_vm<LNWP>();  // that patch's loads (the weights issued after them may fly on)
+          wait_vm<NWP>();  // that patch's loads (the weights issued after them may fly on)
           store_patch(pend_k, pend_c, pv[0]);
           pend_k = -1;
         }
@@ -657,22 +561,11 @@ __device__ __forceinline__ void halo_body(const HaloArgs* args, int prob, int nt
           LSTAMP(l_ld);
           // (in the same branch as the patch loads: on every path the compiler sees NWP DMAs behind
           // them, so its own waits for the staged registers stay at vmcnt(NWP), not vmcnt(0))
-          if constexpr (DW == D && !KSW) {
-#ifndef HALO_ABL_NOW  // TIMING ABLATION (dev builds only, WRONG results): no weight DMAs after the prologue
-            issue_weights(s + D);
-            nnew += NWP;
-#endif
-          }
-        }
-        if constexpr (DW > D && !KSW) {
-          if (s + DW < NS) {
-            issue_weights(s + DW);
-            nnew += NWP;
-          }
+          issue_weights(s + D);
+          nnew += NWP;
         }
         LSTAMP(l_w);
-        // set s+2 has landed: the weight sets issued in the last DW - D super-steps may fly on
-        wait_vm_n(s + 1 < NS ? nnew + (DW - D) * NWP : 0);
+        wait_vm_n(s + 1 < NS ? nnew : 0);  // set s+2 has landed
         __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): a patch stored this super-step is in LDS
         LSTAMP(l_wait);
         __builtin_amdgcn_s_barrier();
@@ -819,15 +712,8 @@ __device__ __forceinline__ void halo_body(const HaloArgs* args, int prob, int nt
   auto split_a = [&](Frag& F) {
 #pragma unroll
     for (int f = 0; f < MF; ++f) {
-#ifdef HALO_ABL_NOSPLIT  // timing ablation (dev builds only): bit casts instead of the split
-      F.ah[f][0] = __builtin_bit_cast(h8, av[f][0]);
-      F.al[f][0] = __builtin_bit_cast(h8, av[f][1]);
-      F.ah[f][1] = __builtin_bit_cast(h8, av[f][2]);
-      F.al[f][1] = __builtin_bit_cast(h8, av[f][3]);
-#else
       split8<X3, BF>(av[f][0], av[f][1], F.ah[f][0], F.al[f][0]);
       split8<X3, BF>(av[f][2], av[f][3], F.ah[f][1], F.al[f][1]);
-#endif
     }
   };
   // the MFMAs of one accumulator never follow each other back to back
@@ -935,55 +821,12 @@ __device__ __forceinline__ void halo_body(const HaloArgs* args, int prob, int nt
     }
   };
 
-  // KS = 2: the even and odd waves of a block hold partial sums of all its outputs.  Each keeps one half (64
-  // columns: even waves columns 0-31, odd 32-63; 32 columns: even waves the block's first tile row, odd the
-  // second), hands the other half to its partner through LDS (the operand rings are free by now: <= 4 KiB per
-  // wave) and stores its half: the block's epilogue runs on both waves of the SIMD.  The sum even + odd is one
-  // fp32 addition per element (commutative: the same bits on either wave).
+  // KS = 2: the even and odd waves of a block hold partial sums of all its outputs.  Each keeps one half
+  // (even waves columns 0-31, odd 32-63), hands the other half to its partner through LDS (the operand rings
+  // are free by now: <= 4 KiB per wave) and stores its half: the block's epilogue runs on both waves of the
+  // SIMD.  The sum even + odd is one fp32 addition per element (commutative: the same bits on either wave).
   auto epilogue_ks2 = [&](const Tile& t) {
-    if constexpr (KS > 1 && NSUB == 1) {
-      if constexpr (X3 && !SC) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[0][0][r] += accx[0][0][r] * (1.0f / SPLIT_SCALE);
-      }
-      // rows r < 8: the first tile row of the block (m < 16); r >= 8 the second
-      f32x4* mine = reinterpret_cast<f32x4*>(smem + (wc * 2 + kp) * 4096) + lane * 2;
-      const f32x4* theirs = reinterpret_cast<const f32x4*>(smem + (wc * 2 + (kp ^ 1)) * 4096) + lane * 2;
-#pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        f32x4 v;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = kp ? acc[0][0][4 * q + i] : acc[0][0][8 + 4 * q + i];
-        mine[q ^ (lane & 1)] = v;
-      }
-      __builtin_amdgcn_s_waitcnt(0xC07F);
-      __builtin_amdgcn_s_barrier();  // (the loaders join it on their way out)
-      f32x16 keep = acc[0][0];
-#pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        const f32x4 o = theirs[q ^ (lane & 1)];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          if (kp)
-            keep[8 + 4 * q + i] += o[i];
-          else
-            keep[4 * q + i] += o[i];
-        }
-      }
-      const int oh = __builtin_amdgcn_readfirstlane(p.out_h), ow = __builtin_amdgcn_readfirstlane(p.out_w);
-      const int rowb = t.b * oh;
-      int rows[16];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int mm = (r & 3) + 8 * (r >> 2) + 4 * h;
-        const int y = t.y0 + 2 * wm + (mm >> 4), x = t.x0 + (mm & 15);
-        rows[r] = ((y < oh) & (x < ow)) ? (rowb + y) * ow + x : -1;
-      }
-      if (kp)
-        tile_epilogue<false, 8, 8>(p, rows, t.n0 + cb + m, keep);
-      else
-        tile_epilogue<false, 0, 8>(p, rows, t.n0 + cb + m, keep);
-    } else if constexpr (KS > 1) {
+    if constexpr (KS > 1) {
       if constexpr (X3 && !SC) {
 #pragma unroll
         for (int sb = 0; sb < NSUB; ++sb)
@@ -1032,42 +875,27 @@ __device__ __forceinline__ void halo_body(const HaloArgs* args, int prob, int nt
   if constexpr (KS > 1) {
     if (kp) advance_a();  // the odd waves' first K-step is K-step 1
   }
-  const WPiecesC wpc = wpieces_c(KSW ? w : 0);
-  if constexpr (KSW) {  // every compute wave issues its pieces of sets 0 .. D-1 (and later of every set)
+  if constexpr (KS > 1) {  // the even compute waves issue the prologue pieces of the 4 loaders
+    if (kp == 0) {
 #pragma unroll
-    for (int u = 0; u < DW; ++u) issue_weights_c(u, wpc);
-    wait_vm<NWPC * (DW - 2)>();
-  } else if constexpr (KS > 1) {  // compute wave w issues the prologue pieces of loader w (4 loaders: the even waves)
-    if (NL == 8 || kp == 0) {
-#pragma unroll
-      for (int u = 0; u < DW; ++u) issue_weights(u);
-      wait_vm<NWP * (DW - 2)>();
+      for (int u = 0; u < D; ++u) issue_weights(u);
+      wait_vm<NWP * (D - 2)>();
     }
   } else if constexpr (NL == 8) {  // (each compute wave also issues the prologue pieces of loader lw + 4)
     const WPieces wp1 = wpieces(lw + 4);
 #pragma unroll
-    for (int u = 0; u < DW; ++u) {
+    for (int u = 0; u < D; ++u) {
       issue_weights(u);
       issue_weights_q(u, wp1);
     }
-    wait_vm<2 * NWP * (DW - 2)>();  // the weights of sets 0 and 1
+    wait_vm<2 * NWP * (D - 2)>();  // the weights of sets 0 and 1
   } else {
 #pragma unroll
-    for (int u = 0; u < DW; ++u) issue_weights(u);
-    wait_vm<NWP * (DW - 2)>();
+    for (int u = 0; u < D; ++u) issue_weights(u);
+    wait_vm<NWP * (D - 2)>();
   }      // the weights of sets 0 and 1 (sets 2 .. D-1: before the first loop barrier)
   __builtin_amdgcn_s_barrier();  // load sets 0 and 1 have landed
-#ifdef HALO_PRIO
-  __builtin_amdgcn_s_setprio(HALO_PRIO);
-#endif
-  // SB1 (KS = 2, dev builds -DHALO_KS2_SB1=1): one fragment buffer per compute wave (each K-step's fragments
-  // read at its start; the partner wave's MFMAs cover the LDS round trip), for the 128 VGPRs of 1024-thread
-  // work-groups
-#ifndef HALO_KS2_SB1
-#define HALO_KS2_SB1 0
-#endif
-  constexpr bool SB1 = KS > 1 && HALO_KS2_SB1;
-  if constexpr (!SB1) first_frags();
+  first_frags();
 #ifdef STAMPS
   unsigned long long t_cmp = 0, t_wait = 0, t_bar = 0, t_epi = 0, t0 = hstamp_now();
   const unsigned long long c_loop = t0;
@@ -1098,38 +926,16 @@ __device__ __forceinline__ void halo_body(const HaloArgs* args, int prob, int nt
   };
   // KS = 2: this wave's U / 2 K-steps of a super-step; PAR: the fragment buffer of its first (the
   // buffers alternate per own K-step, so with one own K-step per super-step the loop runs in pairs)
-  int nnew_c = 0;  // KSW: weight pieces this wave issued in the current super-step
-  auto superstep_ks = [&](auto par_tag, int s) {
+  auto superstep_ks = [&](auto par_tag) {
     constexpr int PAR = decltype(par_tag)::value;
-    nnew_c = 0;
-    if constexpr (KSW) {
-      if (s + D < NS) {
-        issue_weights_c(s + D, wpc);
-        nnew_c = NWPC;
-      }
-    }
 #pragma unroll
-    for (int e = 0; e < U / KS; ++e) {
-      if constexpr (SB1) {
-        __builtin_amdgcn_sched_barrier(0);
-        read_b(F[0]);
-        read_a_split(F[0]);
-        mfma_step(F[0]);
-        __builtin_amdgcn_sched_barrier(0);
-      } else {
-        kstep_split(F[(PAR + e + 1) & 1], F[(PAR + e) & 1]);
-      }
-    }
+    for (int e = 0; e < U / KS; ++e) kstep_split(F[(PAR + e + 1) & 1], F[(PAR + e) & 1]);
   };
   // one super-step's K-steps; LAST: the tile's last super-step, which reads nothing ahead
   auto superstep = [&](auto last_tag) {
     constexpr bool LAST = decltype(last_tag)::value;
 #pragma unroll
     for (int e = 0; e < U; ++e) {
-#ifdef HALO_ABL_MFMAONLY  // timing ablation (dev builds only): MFMAs on fragments read once
-      mfma_step(F[e & 1]);
-      asm volatile("" ::"v"(F[0].ah[0][0]), "v"(F[1].ah[0][0]));
-#else
       if (LAST && e == U - 1) {
         mfma_step(F[e & 1]);
       } else if constexpr (LSPLIT) {
@@ -1140,7 +946,6 @@ __device__ __forceinline__ void halo_body(const HaloArgs* args, int prob, int nt
         split_a(F[(e + 1) & 1]);
         read_a();
       }
-#endif
     }
   };
   bool first = true;
@@ -1153,11 +958,7 @@ __device__ __forceinline__ void halo_body(const HaloArgs* args, int prob, int nt
       __builtin_amdgcn_s_waitcnt(0xC07F | (NRD1 << 8));  // lgkmcnt(NRD1): all but the look-ahead reads
     else
       __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the next fragments are in registers
-    if constexpr (KSW) {
-      wait_vm_n(nnew_c);  // this wave's pieces of every set but the one issued in this super-step have landed
-    } else {
-      if (first) wait_vm<0>();  // the prologue's weight sets 2 .. D-1 (this wave's only DMAs)
-    }
+    if (first) wait_vm<0>();  // the prologue's weight sets 2 .. D-1 (this wave's only DMAs)
     first = false;
 #ifdef STAMPS
     unsigned long long t3 = hstamp_now();
@@ -1175,14 +976,14 @@ __device__ __forceinline__ void halo_body(const HaloArgs* args, int prob, int nt
     int s = 0;
     if constexpr ((U / KS) % 2 == 1) {
       for (; s + 1 < NS; s += 2) {
-        superstep_ks(P0{}, s);
+        superstep_ks(P0{});
         step_end();
-        superstep_ks(P1{}, s + 1);
+        superstep_ks(P1{});
         step_end();
       }
     }
     for (; s < NS; ++s) {
-      superstep_ks(P0{}, s);
+      superstep_ks(P0{});
       step_end();
     }
     __builtin_amdgcn_s_waitcnt(0xC07F);  // (the last look-ahead reads, before the ring is reused)
@@ -1289,12 +1090,6 @@ bool halo_nl8() {
   }
   return v == 8;
 }
-#ifndef HALO_KS2_NL8
-#define HALO_KS2_NL8 0
-#endif
-#ifndef HALO_KS2_BN32  // dev builds: the K-split form for the 32-column update convs too (measured slower: their
-#define HALO_KS2_BN32 0  // 4 K-steps per super-step leave the 4 loaders further behind, profiles/r06b_experiments.txt)
-#endif
 // the K-split form (two compute waves per SIMD, halo_body KS = 2) for the one-tile f16x3 update convs with
 // 64-column tiles (default; RAFT_HALO_KS2=0 or raft_conv2d_set_halo_ks(1): one compute wave per SIMD).
 // Config 2, bench.py interleaved on one box: 144.7 / 143.9 / 144.2 -> 146.9 / 147.0 / 147.0 pairs/s, the
@@ -1359,18 +1154,14 @@ void launch_halo_mt(const HaloLaunch& l, dim3 grid, hipStream_t s, ConvForm* q) 
     }
   }
   // the K-split form: the one-tile f16x3 update convs with 64-column tiles on the pre-split path
-  constexpr bool CAN_KS2 = CAN_NL8 && (BNT == 64 || (BNT == 32 && HALO_KS2_BN32)) &&
-                           HaloCfg<KH, KW, BNT, 128, TH>::D == 3 && !HALO_NOLSPLIT;
+  // (with 32-column tiles it was slower: profiles/r06b_experiments.txt)
+  constexpr bool CAN_KS2 = CAN_NL8 && BNT == 64 && HaloCfg<KH, KW, BNT, 128, TH>::D == 3;
   if (!NO_MT && l.m > 1) {
     halo_start<KH, KW, BNT, PREC, ENC, TH, !NO_MT>(l, grid, s, q);
   } else {
     if constexpr (CAN_KS2) {
       if (halo_ks2()) {
-#if HALO_KS2_NL8  // dev builds: 8 loaders beside the 8 compute waves (1024 threads, 128 VGPRs per wave)
-        halo_start<KH, KW, BNT, PREC, ENC, TH, false, 8, 2>(l, grid, s, q);
-#else
         halo_start<KH, KW, BNT, PREC, ENC, TH, false, 4, 2>(l, grid, s, q);
-#endif
         return;
       }
     }

@@ -80,13 +80,8 @@ __global__ __launch_bounds__(256) void corr_build_kernel(CorrBuildArgs a) {
       const bool cin = kc * CB_BK + lq * 4 < a.C;  // C % 4 == 0; zero-fill the K tail
       ok_a[i] = av_[i] && cin;
       ok_b[i] = bv_[i] && cin;
-#ifdef CB_ABL_NOGLOAD
-      ra[i] = f32x4{(float)kc, 1.f, 2.f, (float)i};
-      rb[i] = f32x4{(float)i, 1.f, 2.f, (float)kc};
-#else
       ra[i] = *reinterpret_cast<const f32x4*>(ok_a[i] ? arow[i] + kc * CB_BK : a.f1);
       rb[i] = *reinterpret_cast<const f32x4*>(ok_b[i] ? brow[i] + kc * CB_BK : a.f2);
-#endif
     }
   };
   auto sstore = [&](int buf) {
@@ -268,13 +263,8 @@ __global__ __launch_bounds__(512, 2) void corr_build2_kernel(CorrBuildArgs a) {
       const bool cin = kc * CB_BK + lq * 4 < a.C;  // C % 4 == 0; zero-fill the K tail
       ok_a[i] = av_[i] && cin;
       ok_b[i] = bv_[i] && cin;
-#ifdef CB_ABL_NOGLOAD
-      ra[i] = f32x4{(float)kc, 1.f, 2.f, (float)i};
-      rb[i] = f32x4{(float)i, 1.f, 2.f, (float)kc};
-#else
       ra[i] = *reinterpret_cast<const f32x4*>(ok_a[i] ? arow[i] + kc * CB_BK : a.f1);
       rb[i] = *reinterpret_cast<const f32x4*>(ok_b[i] ? brow[i] + kc * CB_BK : a.f2);
-#endif
     }
   };
   auto put = [&](float* base, int row, f32x4 v) {
@@ -306,11 +296,7 @@ __global__ __launch_bounds__(512, 2) void corr_build2_kernel(CorrBuildArgs a) {
   f32x16 acc[2] = {}, accl[2] = {};  // hi*hi | lo*hi + hi*lo
   for (int kc = 0; kc < nk; ++kc) {
     const int cur = kc & 1;
-#ifdef CB_ABL_NOLOAD
-    const bool more = false;
-#else
     const bool more = kc + 1 < nk;
-#endif
     if (more) gload(kc + 1);
     const float* A = smem + cur * STAGE;
     const float* Bt = A + CB2_BM * CB_LDSK;
@@ -323,13 +309,9 @@ __global__ __launch_bounds__(512, 2) void corr_build2_kernel(CorrBuildArgs a) {
         const char* Br = reinterpret_cast<const char*>(Bt) + (wn * 64 + sb * 32 + (lane & 31)) * (CB_LDSK * 4) +
                          (lane >> 5) * 16;
         const h8 yh = *reinterpret_cast<const h8*>(Br + 32 * qq), yl = *reinterpret_cast<const h8*>(Br + 64 + 32 * qq);
-#ifdef CB_ABL_NOMFMA
-        acc[sb][0] += (float)xh[0] * (float)yh[0] + (float)xl[1] * (float)yl[2];
-#else
         acc[sb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(xh, yh, acc[sb], 0, 0, 0);
         accl[sb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(xl, yh, accl[sb], 0, 0, 0);
         accl[sb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(xh, yl, accl[sb], 0, 0, 0);
-#endif
       }
     }
     if (more) sstore(cur ^ 1);
@@ -355,11 +337,7 @@ __global__ __launch_bounds__(512, 2) void corr_build2_kernel(CorrBuildArgs a) {
     const int p1 = m0 + row;
     const int ti = o >> 6, tj = (o >> 4) & 3, e = o & 15;
     const int ty = 2 * by + ti, tx = 4 * bx + tj;
-#ifdef CB_ABL_NOSTORE
-    if (p1 < a.P && ty < a.l0.th && tx < a.l0.tw && p1 < 0) {
-#else
     if (p1 < a.P && ty < a.l0.th && tx < a.l0.tw) {
-#endif
       // one conflict-free ds_read_b128 (row stride 132 floats)
       const f32x4 v = *reinterpret_cast<const f32x4*>(T + row * CB2_TLD + (ti * 4 + (e >> 2)) * 16 + tj * 4);
       f32x4* dst = reinterpret_cast<f32x4*>(a.pyr + a.l0.off + ((long)b * a.P + p1) * a.l0.mapsz +
@@ -379,9 +357,6 @@ __global__ __launch_bounds__(512, 2) void corr_build2_kernel(CorrBuildArgs a) {
       const int tj = o >> 4, e = o & 15;
       const int tx1 = 2 * bx + tj;
       if (p1 >= a.P || tx1 >= a.l1.tw) continue;
-#ifdef CB_ABL_NOSTORE
-      if (p1 >= 0) continue;
-#endif
       const int yy = e >> 2;
       f32x4 v4;
 #pragma unroll
@@ -1033,11 +1008,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void c
       rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(mapb), (short)0, (int)(lv.mapsz * 4), 0x00020000);
       off = ok ? ((__umul24((unsigned)ty, (unsigned)lv.tw) + (unsigned)tx) * 64u + (unsigned)(rr * 16)) : 0x80000000u;
     }
-#ifdef LK_ABL_NOLOAD  // timing ablation (dev builds only): no tile loads
-    v[k] = f32x4{(float)off, 0.f, 0.f, 0.f};
-#else
     v[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0));
-#endif
   }
 
   LK_STAMP(2);
@@ -1138,9 +1109,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void c
     for (int iy = 1; iy < RD; ++iy) mx = fmaxf(mx, fabsf(val[iy]));
     if (mx > RAFT_RANGE_LIMIT) *a.range_flag = 1;
   }
-#ifdef LK_ABL_NOSTORE  // timing ablation (dev builds only): no output stores
-  if (val[0] != -12345.f) return;
-#endif
   const bool vec_out = a.out_layout == 0 && (a.out_ld & 3) == 0 && (ntap & 3) == 0 && ((uintptr_t)a.out & 15) == 0;
   if (vec_out) {
     // NHWC row: transpose the columns through this wave's (consumed) patch

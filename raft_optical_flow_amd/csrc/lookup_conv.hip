@@ -138,18 +138,8 @@ __global__ __launch_bounds__(512) void lookup_conv_kernel(LookupConvArgs g) {
   const int H = a.H, W = a.W, P = H * W;
 
   // The K stream of step 4, in registers: convc1's 11 K-steps (all waves) then convf1's 4 (waves
-  // 0-3), prefetched PF steps ahead.  LC_EARLY: the first PF steps are issued here, before the coords
-  // load, so that the weight bytes (the whole 360 KB split convc1 weight per work-group) stream in
-  // under the coords / window-tile round trips and the taps instead of after them.
-#ifndef LC_PF
-#define LC_PF 3
-#endif
-#ifndef LC_TAPS2
-#define LC_TAPS2 1
-#endif
-#ifndef LC_A1EARLY
-#define LC_A1EARLY 0
-#endif
+  // 0-3), prefetched PF steps ahead (the first PF steps are issued in step 3, behind the window tiles).
+  constexpr int LC_PF = 3;
   constexpr int PF = LC_PF;
   h8 wb[PF + 1][NT];
   auto load_w = [&](int j, h8 (&dst)[NT]) {
@@ -192,12 +182,6 @@ __global__ __launch_bounds__(512) void lookup_conv_kernel(LookupConvArgs g) {
 #pragma unroll
     for (int k = 1; k < LC_PX; ++k) gk = (lane & 3) == k ? px_gp[k] : gk;
     const float cx = a.coords[2L * gk], cy = a.coords[2L * gk + 1];
-#ifdef LC_EARLY  // (behind the coords load: its wait leaves the weight loads in flight)
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int j = 0; j < PF; ++j) load_w(j, wb[j]);
-    __builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
     for (int k = 0; k < LC_PX; ++k) {
       px_x[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cx), k));
@@ -227,10 +211,7 @@ __global__ __launch_bounds__(512) void lookup_conv_kernel(LookupConvArgs g) {
   const float f1b = (wv < 4 && g.f1bias) ? g.f1bias[32 * wv + m] : 0.f;
   // (their waits here, behind the coords' round trip: after the window loads the compiler, which
   // cannot count the loads of the two window paths below as equal, would wait for all of them)
-#ifndef LC_EARLYWAIT
-#define LC_EARLYWAIT 1
-#endif
-  if constexpr (LC_EARLYWAIT != 0) asm volatile("" ::"v"(prm), "v"(c1b), "v"(f1b), "v"(fc));
+  asm volatile("" ::"v"(prm), "v"(c1b), "v"(f1b), "v"(fc));
 
   __builtin_amdgcn_sched_barrier(0);
   f32x4 v[LC_PX][LC_L];
@@ -238,13 +219,7 @@ __global__ __launch_bounds__(512) void lookup_conv_kernel(LookupConvArgs g) {
   // offsets, the window test per lane on the VALU.  Per (pixel, level) the scalar unit then computes
   // only the window origin and one product (~12 SALU instead of ~46 with a 64-bit base and a resource
   // per window: the scalar unit, shared by the CU's 8 waves, was the tile-issue phase's limit).
-#ifndef LC_OFF32
-#define LC_OFF32 1
-#endif
-#ifndef LC_TAB
-#define LC_TAB 1
-#endif
-  bool off32 = LC_OFF32 != 0;
+  bool off32 = true;
   const unsigned nmaps = (unsigned)(a.B * P);
 #pragma unroll
   for (int l = 0; l < LC_L; ++l) off32 &= (unsigned long long)nmaps * lmsz[l] * 4ull < 0x7FFFFFF0ull;
@@ -258,7 +233,6 @@ __global__ __launch_bounds__(512) void lookup_conv_kernel(LookupConvArgs g) {
       lano[l] = __umul24((unsigned)ti, (unsigned)(64 * ltw[l])) + 16u * (unsigned)(lane & 15);
       lmsz4[l] = lmsz[l] * 4u;
     }
-#if LC_TAB
     // The 16 (pixel, level) windows' parameters computed once, window (k, l) on lane 4k + l, on the VALU,
     // and read back per load (3 v_readlane): the window's origin offset and its row / tile-column
     // intervals clipped to the map (relative to the lane's row / column in the window, 16 + 16 bits).
@@ -309,32 +283,7 @@ __global__ __launch_bounds__(512) void lookup_conv_kernel(LookupConvArgs g) {
         v[k][l] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsl[l], off, 0, 0));
       }
     }
-#else
-#pragma unroll
-    for (int k = 0; k < LC_PX; ++k) {
-      const unsigned gp = (unsigned)px_gp[k];
-      const int xf = __builtin_amdgcn_readfirstlane(floor_origin(px_x[k]));
-      const int yf = __builtin_amdgcn_readfirstlane(floor_origin(px_y[k]));
-#pragma unroll
-      for (int l = 0; l < LC_L; ++l) {
-        const int wx0 = (xf >> l) - R, wy0 = (yf >> l) - R;
-        const int tyo = wy0 >> 2, txo = wx0 >> 2;
-        const int ntx = ((wx0 + WD - 1) >> 2) - txo + 1;
-        // map row / tile column this lane reads; inside the window and the map, or no access (tests
-        // combined bitwise and the offset selected: no branch around the load)
-        const int rowm = 4 * tyo + lrow, colt = txo + tj;
-        const bool tok = px_ok[k] & ((unsigned)(rowm - wy0) < (unsigned)WD) & ((unsigned)rowm < (unsigned)(4 * lth[l])) &
-                         ((unsigned)tj < (unsigned)ntx) & ((unsigned)colt < (unsigned)ltw[l]);
-        const unsigned sb = gp * lmsz4[l] + (unsigned)(tyo * ltw[l] + txo) * 64u;
-        unsigned offv = sb + lano[l];
-        asm volatile("" : "+v"(offv));  // (computed for every lane: a select, not a branch around it)
-        const unsigned off = tok ? offv : 0x80000000u;
-        v[k][l] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsl[l], off, 0, 0));
-      }
-    }
-#endif
   } else {
-#if LC_TAB
     // (pyramids past 2^31 bytes per level, e.g. config 5: 4.2 GB of level 0) the same table with each
     // window's 64-bit base address instead of the 32-bit offset (4 v_readlane per load, a resource per
     // window as before)
@@ -392,33 +341,6 @@ __global__ __launch_bounds__(512) void lookup_conv_kernel(LookupConvArgs g) {
         v[k][l] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0));
       }
     }
-#else
-#pragma unroll
-  for (int k = 0; k < LC_PX; ++k) {
-    const bool ok = px_ok[k];
-    const int gp = px_gp[k];
-    const int xf = __builtin_amdgcn_readfirstlane(floor_origin(px_x[k]));
-    const int yf = __builtin_amdgcn_readfirstlane(floor_origin(px_y[k]));
-#pragma unroll
-    for (int l = 0; l < LC_L; ++l) {
-      const int wx0 = (xf >> l) - R, wy0 = (yf >> l) - R;
-      const int tyo = wy0 >> 2, txo = wx0 >> 2;
-      const int ntx = ((wx0 + WD - 1) >> 2) - txo + 1;
-      // (the scalar-interval window test of corr_lookup_kernel<..., SCAL>)
-      const int rlo = max(wy0, 0), rhi = min(wy0 + WD, 4 * lth[l]);
-      const int clo = max(txo, 0), chi = min(txo + ntx, ltw[l]);
-      const int rb = __builtin_amdgcn_readfirstlane(rlo - 4 * tyo), cb = __builtin_amdgcn_readfirstlane(clo - txo);
-      const bool tok = ok && ((unsigned)(lrow - rb) < (unsigned)max(rhi - rlo, 0)) &&
-                       ((unsigned)(tj - cb) < (unsigned)max(chi - clo, 0));
-      const float* wbase = lbs[l] + (long)((unsigned long long)(unsigned)gp * lmsz[l]) + ((long)tyo * ltw[l] + txo) * 16;
-      const __amdgpu_buffer_rsrc_t rs =
-          __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(wbase), (short)0, 0x7FFFFFFF, 0x00020000);
-      const unsigned off = tok ? __umul24((unsigned)ti, (unsigned)(64 * ltw[l])) + 16u * (unsigned)(lane & 15)
-                               : 0x80000000u;
-      v[k][l] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0));
-    }
-  }
-#endif
   }
   LC_STAMP(1);
   // ---- 2. while the tiles fly: the per-axis sampling entries of the four pixels ------------
@@ -451,37 +373,12 @@ __global__ __launch_bounds__(512) void lookup_conv_kernel(LookupConvArgs g) {
     fl[fi] = fv;
   }
   LC_STAMP(2);
-#if LC_A1EARLY
-  // convf1's A operand before the taps, while the window tiles are still in flight
-  __syncthreads();  // the flow patch is visible
-  // convf1's im2col A operand: row mm, K = 2 (dy*7 + dx) + ci (the GATHER packing), 8 K per thread
-  {
-    const int mm = threadIdx.x >> 4, q = threadIdx.x & 15;
-    const int py = mm >> 4, px = mm & 15;
-    float e[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int k = 8 * q + i, t = k >> 1;
-      const int dy = t / LC_F1K, dx = t - dy * LC_F1K;
-      const float2 fv = fl[(py + (k < 2 * LC_F1KK ? dy : 0)) * LC_FPW + px + (k < 2 * LC_F1KK ? dx : 0)];
-      e[i] = k < 2 * LC_F1KK ? ((k & 1) ? fv.y : fv.x) : 0.f;
-    }
-    h8 hi, lo;
-    split8<X3, BF>(f32x4{e[0], e[1], e[2], e[3]}, f32x4{e[4], e[5], e[6], e[7]}, hi, lo);
-    const int j = q >> 2, qd = q & 3, sw = (mm >> 1) & 7;
-    char* row = smem + LC_OFF_A1 + j * (LC_M * 128) + mm * 128;
-    *reinterpret_cast<h8*>(row + ((qd ^ sw) << 4)) = hi;
-    if constexpr (X3) *reinterpret_cast<h8*>(row + (((4 + qd) ^ sw) << 4)) = lo;
-  }
-#endif
 
   // ---- 3. the taps of each pixel -> split rows of convc1's A operand ------------------------
-  // (default: the first PF K-steps of the weight stream are issued here, behind the tiles, so they
+  // (the first PF K-steps of the weight stream are issued here, behind the tiles, so they
   // land during the taps)
-#ifndef LC_EARLY
 #pragma unroll
   for (int j = 0; j < PF; ++j) load_w(j, wb[j]);
-#endif
   char* Abase = smem;
   bool big = false;
   auto patch_of = [&](int k) {
@@ -501,10 +398,6 @@ __global__ __launch_bounds__(512) void lookup_conv_kernel(LookupConvArgs g) {
         const char* p0 = reinterpret_cast<const char*>(&patch[pidx<4>(0, xwk, l)]);
         const char* p1 = reinterpret_cast<const char*>(&patch[pidx<4>(0, xwk + 1, l)]);
         auto at = [](const char* bp, int byte) { return *reinterpret_cast<const float*>(bp + byte); };
-#ifndef LC_TAPS3
-#define LC_TAPS3 1
-#endif
-#if LC_TAPS3 && LC_TAPS2
         // The nine y-entries first.  Where every lane's nine rows are consecutive (the common case: the float
         // round trip moved no floor), tap iy's lower row is tap iy + 1's upper row: the lane reads its two
         // columns once, RD + 1 rows each (10 LDS reads of two rows, 4 * RS bytes apart, instead of 18), and
@@ -545,35 +438,6 @@ __global__ __launch_bounds__(512) void lookup_conv_kernel(LookupConvArgs g) {
             val[iy] = fmaf(sS, hh.x, ty * hh.y);
           }
         }
-#else
-#pragma unroll
-        for (int iy = 0; iy < RD; ++iy) {
-#if LC_TAPS2
-          // (8 of the entry's 16 bytes: one ds_read_b64, 2 LDS cycles, instead of a b96 read's 8; 1 - ty
-          // is the same fp32 subtraction axis_entry stored)
-          const int2 ye = *reinterpret_cast<const int2*>(&yt[l * RD + iy]);
-          const int ro = ye.x;
-          const float ty = __int_as_float(ye.y), sS = 1.0f - ty;
-#else
-          const int4 ye = yt[l * RD + iy];
-          const int ro = ye.x;
-          const float ty = __int_as_float(ye.y), sS = __int_as_float(ye.z);
-#endif
-          const f32x2 c0 = {at(p0, ro), at(p0, ro + 4 * RS)}, c1 = {at(p1, ro), at(p1, ro + 4 * RS)};
-          const f32x2 hh = __builtin_elementwise_fma(c0, (f32x2){ex, ex}, c1 * (f32x2){xt[k], xt[k]});
-          val[iy] = fmaf(sS, hh.x, ty * hh.y);
-        }
-#ifndef LC_TAPSGB
-#define LC_TAPSGB 1
-#endif
-#if LC_TAPSGB && LC_TAPS2
-        // the nine y-entries read first, then every tap's corner pairs, then the arithmetic: one LDS round
-        // trip per phase instead of one per tap (the compiler had waited after each tap's reads)
-        __builtin_amdgcn_sched_group_barrier(0x100, RD, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 2 * RD, 0);
-        __builtin_amdgcn_sched_group_barrier(0x002, 4 * RD, 0);
-#endif
-#endif  // LC_TAPS3
       }
     } else if (col) {
       unsigned deferred = 0;
@@ -616,7 +480,6 @@ __global__ __launch_bounds__(512) void lookup_conv_kernel(LookupConvArgs g) {
   auto write_row = [&](int k, const float (&val)[RD]) {
     const int mk = LC_PX * wv + k;
     const int sw = (mk >> 1) & 7;
-#if LC_TAPS2
     // the lane's nine consecutive channels as four 4-B writes of channel pairs (c even, c + 1: one
     // f16 pair of one quad) and one 2-B write, per half: 10 LDS writes instead of 18
     if (col) {
@@ -650,22 +513,6 @@ __global__ __launch_bounds__(512) void lookup_conv_kernel(LookupConvArgs g) {
         if constexpr (X3) *reinterpret_cast<_Float16*>(at_c(c, 1)) = ls;
       }
     } else if (lane - LC_L * RD < 32 * LC_KS - LC_NTAP) {
-#else
-    if (col) {
-#pragma unroll
-      for (int iy = 0; iy < RD; ++iy) {
-        const float vv = px_ok[k] ? val[iy] : 0.f;
-        big |= fabsf(vv) > RAFT_RANGE_LIMIT;
-        const int c = cbase + iy;
-        const int j = c >> 5, kk = c & 31;
-        _Float16 hi, lo;
-        split1<X3, BF>(vv, hi, lo);
-        char* rb = Abase + j * (LC_M * 128) + mk * 128;
-        *reinterpret_cast<_Float16*>(rb + (((kk >> 3) ^ sw) << 4) + 2 * (kk & 7)) = hi;
-        if constexpr (X3) *reinterpret_cast<_Float16*>(rb + (((4 + (kk >> 3)) ^ sw) << 4) + 2 * (kk & 7)) = lo;
-      }
-    } else if (lane - LC_L * RD < 32 * LC_KS - LC_NTAP) {
-#endif
       const int c = LC_NTAP + lane - LC_L * RD;
       const int j = c >> 5, kk = c & 31;
       char* rb = Abase + j * (LC_M * 128) + mk * 128;
@@ -696,9 +543,6 @@ __global__ __launch_bounds__(512) void lookup_conv_kernel(LookupConvArgs g) {
   }
   if (a.range_flag && big) *a.range_flag = 1;
   LC_STAMP(3);
-#if LC_A1EARLY
-  __syncthreads();  // every A row is in LDS
-#else
   __syncthreads();  // the flow patch is visible
   // convf1's im2col A operand: row mm, K = 2 (dy*7 + dx) + ci (the GATHER packing), 8 K per thread
   {
@@ -720,121 +564,79 @@ __global__ __launch_bounds__(512) void lookup_conv_kernel(LookupConvArgs g) {
     if constexpr (X3) *reinterpret_cast<h8*>(row + (((4 + qd) ^ sw) << 4)) = lo;
   }
   __syncthreads();  // every A row is in LDS
-#endif
   LC_STAMP(4);
 
   // ---- 4. convc1 (all waves, 32 outputs each) then convf1 (waves 0-3) on MFMA: one K stream ----
   const int sw = (m >> 1) & 7;
-  auto kstep = [&](const char* A, const h8 (&B)[NT], f32x16& c, f32x16& cx) {
-    const char* row = A + m * 128;
+  f32x16 acc = {}, accx = {}, facc = {}, faccx = {};
+  const bool f1w = wv < LC_F1N / 32;  // (wave-uniform)
+  // The K stream with its schedule pinned (one scheduling region per K-step): the weight loads of step
+  // j + PF first, then the A fragments of step j + 1 from LDS one per MFMA gap beside step j's MFMAs.  Left
+  // to itself the compiler sank both to just before their use (a vmcnt / lgkmcnt wait per MFMA pair: the L2
+  // round trip of every weight K-step exposed).  Every statement is unconditional so a step is one basic
+  // block: waves 4-7 load convf1's weight addresses of wave 3 and read its A operand without using them.
+  struct AF {
     h8 ah[2], al[2];
+  };
+  auto read_af = [&](const char* A, AF& f) {
+    const char* row = A + m * 128;
 #pragma unroll
     for (int qq = 0; qq < 2; ++qq) {
-      ah[qq] = *reinterpret_cast<const h8*>(row + (((2 * h + qq) ^ sw) << 4));
-      if constexpr (X3) al[qq] = *reinterpret_cast<const h8*>(row + (((4 + 2 * h + qq) ^ sw) << 4));
+      f.ah[qq] = *reinterpret_cast<const h8*>(row + (((2 * h + qq) ^ sw) << 4));
+      if constexpr (X3) f.al[qq] = *reinterpret_cast<const h8*>(row + (((4 + 2 * h + qq) ^ sw) << 4));
     }
+  };
+  auto mfma_af = [&](const AF& f, const h8 (&B)[NT], f32x16& c, f32x16& cx) {
 #pragma unroll
     for (int qq = 0; qq < 2; ++qq) {
       if constexpr (BF) {
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf8, ah[qq]), __builtin_bit_cast(bf8, B[qq]), c,
-                                                    0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf8, f.ah[qq]), __builtin_bit_cast(bf8, B[qq]),
+                                                    c, 0, 0, 0);
       } else {
-        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[qq], B[qq], c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.ah[qq], B[qq], c, 0, 0, 0);
       }
       if constexpr (X3) {
-        cx = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[qq], B[2 + qq], cx, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[qq], B[qq], c, 0, 0, 0);
+        cx = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.ah[qq], B[2 + qq], cx, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.al[qq], B[qq], c, 0, 0, 0);
       }
     }
   };
-  f32x16 acc = {}, accx = {}, facc = {}, faccx = {};
-  const bool f1w = wv < LC_F1N / 32;  // (wave-uniform)
-#ifndef LC_SGB
-#define LC_SGB 1
-#endif
-  if constexpr (LC_SGB) {
-    // The K stream with its schedule pinned (one scheduling region per K-step): the weight loads of step
-    // j + PF first, then the A fragments of step j + 1 from LDS one per MFMA gap beside step j's MFMAs.  Left
-    // to itself the compiler sank both to just before their use (a vmcnt / lgkmcnt wait per MFMA pair: the L2
-    // round trip of every weight K-step exposed).  Every statement is unconditional so a step is one basic
-    // block: waves 4-7 load convf1's weight addresses of wave 3 and read its A operand without using them.
-    struct AF {
-      h8 ah[2], al[2];
-    };
-    auto read_af = [&](const char* A, AF& f) {
-      const char* row = A + m * 128;
+  auto load_w_any = [&](int j, h8 (&dst)[NT]) {  // (waves 4-7: convf1's steps of wave 3, unused)
+    const int wq = j < LC_KS ? wv : (wv < LC_F1N / 32 ? wv : LC_F1N / 32 - 1);
+    const h8* wf = j < LC_KS ? g.wfrag + ((j * (LC_N / 32) + wq) * 4) * 64
+                             : g.f1frag + (((j - LC_KS) * (LC_F1N / 32) + wq) * 4) * 64;
 #pragma unroll
-      for (int qq = 0; qq < 2; ++qq) {
-        f.ah[qq] = *reinterpret_cast<const h8*>(row + (((2 * h + qq) ^ sw) << 4));
-        if constexpr (X3) f.al[qq] = *reinterpret_cast<const h8*>(row + (((4 + 2 * h + qq) ^ sw) << 4));
-      }
-    };
-    auto mfma_af = [&](const AF& f, const h8 (&B)[NT], f32x16& c, f32x16& cx) {
+    for (int t = 0; t < NT; ++t) dst[t] = wf[t * 64 + lane];
+  };
+  constexpr int NRA = X3 ? 4 : 2, NMA = X3 ? 6 : 2;
+  auto groups = [&](bool loads) {
+    if (loads) __builtin_amdgcn_sched_group_barrier(0x020, NT, 0);  // the weight loads first
 #pragma unroll
-      for (int qq = 0; qq < 2; ++qq) {
-        if constexpr (BF) {
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf8, f.ah[qq]), __builtin_bit_cast(bf8, B[qq]),
-                                                      c, 0, 0, 0);
-        } else {
-          c = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.ah[qq], B[qq], c, 0, 0, 0);
-        }
-        if constexpr (X3) {
-          cx = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.ah[qq], B[2 + qq], cx, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.al[qq], B[qq], c, 0, 0, 0);
-        }
-      }
-    };
-    auto load_w_any = [&](int j, h8 (&dst)[NT]) {  // (waves 4-7: convf1's steps of wave 3, unused)
-      const int wq = j < LC_KS ? wv : (wv < LC_F1N / 32 ? wv : LC_F1N / 32 - 1);
-      const h8* wf = j < LC_KS ? g.wfrag + ((j * (LC_N / 32) + wq) * 4) * 64
-                               : g.f1frag + (((j - LC_KS) * (LC_F1N / 32) + wq) * 4) * 64;
-#pragma unroll
-      for (int t = 0; t < NT; ++t) dst[t] = wf[t * 64 + lane];
-    };
-    constexpr int NRA = X3 ? 4 : 2, NMA = X3 ? 6 : 2;
-    auto groups = [&](bool loads) {
-      if (loads) __builtin_amdgcn_sched_group_barrier(0x020, NT, 0);  // the weight loads first
-#pragma unroll
-      for (int i = 0; i < NMA; ++i) {
-        if (i < NRA) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      }
-    };
-    AF af[2];
-    read_af(Abase, af[0]);
-#pragma unroll
-    for (int j = 0; j < LC_KS; ++j) {
-      __builtin_amdgcn_sched_barrier(0);
-      if (j + PF < LC_KS + LC_F1KS) load_w_any(j + PF, wb[(j + PF) % (PF + 1)]);
-      read_af(j + 1 < LC_KS ? Abase + (j + 1) * (LC_M * 128) : smem + LC_OFF_A1, af[(j + 1) & 1]);
-      mfma_af(af[j & 1], wb[j % (PF + 1)], acc, accx);
-      groups(j + PF < LC_KS + LC_F1KS);
-      __builtin_amdgcn_sched_barrier(0);
+    for (int i = 0; i < NMA; ++i) {
+      if (i < NRA) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
     }
-    if (f1w) {
-#pragma unroll
-      for (int j = LC_KS; j < LC_KS + LC_F1KS; ++j) {
-        __builtin_amdgcn_sched_barrier(0);
-        if (j + PF < LC_KS + LC_F1KS) load_w_any(j + PF, wb[(j + PF) % (PF + 1)]);
-        if (j + 1 < LC_KS + LC_F1KS) read_af(smem + LC_OFF_A1 + (j + 1 - LC_KS) * (LC_M * 128), af[(j + 1) & 1]);
-        mfma_af(af[j & 1], wb[j % (PF + 1)], facc, faccx);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-  } else {
+  };
+  AF af[2];
+  read_af(Abase, af[0]);
 #pragma unroll
   for (int j = 0; j < LC_KS; ++j) {
-    // (the K stream continues into convf1's steps on waves 0-3)
-    if (j + PF < LC_KS || f1w) load_w(j + PF, wb[(j + PF) % (PF + 1)]);
-    kstep(Abase + j * (LC_M * 128), wb[j % (PF + 1)], acc, accx);
+    __builtin_amdgcn_sched_barrier(0);
+    if (j + PF < LC_KS + LC_F1KS) load_w_any(j + PF, wb[(j + PF) % (PF + 1)]);
+    read_af(j + 1 < LC_KS ? Abase + (j + 1) * (LC_M * 128) : smem + LC_OFF_A1, af[(j + 1) & 1]);
+    mfma_af(af[j & 1], wb[j % (PF + 1)], acc, accx);
+    groups(j + PF < LC_KS + LC_F1KS);
+    __builtin_amdgcn_sched_barrier(0);
   }
   if (f1w) {
 #pragma unroll
     for (int j = LC_KS; j < LC_KS + LC_F1KS; ++j) {
-      if (j + PF < LC_KS + LC_F1KS) load_w(j + PF, wb[(j + PF) % (PF + 1)]);
-      kstep(smem + LC_OFF_A1 + (j - LC_KS) * (LC_M * 128), wb[j % (PF + 1)], facc, faccx);
+      __builtin_amdgcn_sched_barrier(0);
+      if (j + PF < LC_KS + LC_F1KS) load_w_any(j + PF, wb[(j + PF) % (PF + 1)]);
+      if (j + 1 < LC_KS + LC_F1KS) read_af(smem + LC_OFF_A1 + (j + 1 - LC_KS) * (LC_M * 128), af[(j + 1) & 1]);
+      mfma_af(af[j & 1], wb[j % (PF + 1)], facc, faccx);
+      __builtin_amdgcn_sched_barrier(0);
     }
-  }
   }
   if constexpr (X3) {
 #pragma unroll
@@ -871,10 +673,6 @@ __global__ __launch_bounds__(512) void lookup_conv_kernel(LookupConvArgs g) {
     if (threadIdx.x == 0)
       atomicMax(&g_lc_span[2 * g.span_slot + 1], (unsigned long long)__builtin_amdgcn_s_memrealtime());
   }
-#ifdef LC_END_FENCE  // dev experiment: agent-scope release of the outputs before the waves exit
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-  __builtin_amdgcn_s_waitcnt(0);
-#endif
 #ifdef LC_STAMPS
   __builtin_amdgcn_s_waitcnt(0);
   LC_STAMP(6);
