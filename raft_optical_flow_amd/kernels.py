@@ -7,7 +7,6 @@ capture.  Every function launches hand-written HIP kernels on
 from __future__ import annotations
 
 import ctypes
-import math
 from collections import OrderedDict
 from dataclasses import dataclass
 
@@ -33,12 +32,6 @@ def require_device(*tensors):
                                f"{t.device} (no CPU fallback)")
         if t.dtype != torch.float32:
             raise TypeError(f"raft_optical_flow_amd kernels take float32 tensors, got {t.dtype}")
-
-
-def ptr(t: torch.Tensor | None, offset_floats: int = 0) -> int | None:
-    if t is None:
-        return None
-    return t.data_ptr() + 4 * offset_floats
 
 
 class Rows:
@@ -390,6 +383,3 @@ def sqrt_c(c: int) -> float:
 def instnorm_workspace(b, hw, c, device):
     n = int(_lib.load().raft_instnorm_workspace_floats(b, hw, c))
     return torch.empty(max(n, 1), device=device, dtype=torch.float32)
-
-
-__all__ = [n for n in dir() if not n.startswith("_")] + ["math"]

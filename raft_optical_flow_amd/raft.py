@@ -281,13 +281,8 @@ class RAFT(nn.Module):
                       RuntimeWarning)
         i1, i2, fi = rec["inputs"]
         exact = self.forward(i1, i2, rec["iters"], fi, True, rec["test_mode"], _prec="fp32")
-        outs, new = rec["outputs"], exact
-        if isinstance(outs, tuple):
-            for o, n in zip(outs, new):
-                o.copy_(n)
-        else:
-            for o, n in zip(outs, new):
-                o.copy_(n)
+        for o, n in zip(rec["outputs"], exact):   # (low, up) or the list of upsampled flows
+            o.copy_(n)
 
     def forward(self, image1, image2, iters=12, flow_init=None, upsample=True, test_mode=False, _prec=None):
         if image1.is_cuda and image1.device != torch.device("cuda", torch.cuda.current_device()):

@@ -38,7 +38,7 @@ def pack_lookup_conv_weights(wc, bc, wf, bf, prec):
     from raft_optical_flow_amd import _lib
     from raft_optical_flow_amd import kernels as K
     p = _lib.PRECISIONS[prec]
-    # convc1 weights, packed as the engine does (engine.convc1_frag_weight)
+    # convc1 weights, packed as the engine does (engine.frag_weight)
     pc = K.pack_conv(torch.from_numpy(wc)[:, :, None, None], torch.from_numpy(bc), 1, 0, device=DEV)
     pc.precision = p
     split = pc.launch_weight()
