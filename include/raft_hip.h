@@ -731,6 +731,76 @@ int raft_flow_to_rgb(const float* flow, long batch_stride, long chan_stride, lon
                      long frame_batch_stride, long frame_chan_stride, long frame_pitch, float* ws,
                      unsigned char* out, raft_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * Warping by a flow field (utils.warp_frame, utils.splat_density, RAFT.stream(warp=...)).
+ * Additive entries: RAFT_HIP_ABI_VERSION stays 19.
+ * --------------------------------------------------------------------------- */
+/* Backward warp: out(x) = bilinear sample of the frame at x + flow(x), all B images and C channels in one
+ * launch, and valid(x) = whether that position lies in the frame.  With flow = the flow from frame 1 to
+ * frame 2 and frame = frame 2, out is frame 2 pulled back onto frame 1.
+ *
+ * Definition.  At pixel (j, i) of the H x W frame the displacement is d = (dx, dy) = flow(j, i) (channel
+ * 0 = x, channel 1 = y, in pixels).
+ *   axes      each axis as raft_fb_consistency takes it: fl = floor(d), t = d - fl, i0 = j + (int)fl
+ *             (x: base x0, weight ax; y: base y0, weight ay).  t is exact in fp32 but for one rounding of
+ *             <= 2^-25 where -1 < d < 0; the sum j + d is never formed.
+ *   rejected  dx or dy not finite, or |d| >= 2^30 on either axis: every channel of out is 0 and
+ *             valid = 0, in both modes.
+ *   valid     1 iff the position lies in [0, W-1] x [0, H-1]: per axis i0 >= 0 and (i0 < n-1, or
+ *             i0 == n-1 with t == 0) -- the `inside` of raft_fb_consistency.  The same in both modes.
+ *   zeros     (the default) the taps are (y0, x0), (y0, x0+1), (y0+1, x0), (y0+1, x0+1); a tap outside
+ *             the H x W crop contributes 0 and is not read.  A position in (-1, 0) or (n-1, n) still
+ *             blends its inside taps with their weights, as grid_sample(padding_mode='zeros',
+ *             align_corners=True) does.
+ *   border    (RAFT_WARP_BORDER) per axis, before the taps are taken: i0 < 0 gives i0 = 0, t = 0;
+ *             i0 >= n-1 gives i0 = n-1, t = 0 (grid_sample's padding_mode='border').  The +1 tap of a
+ *             clamped axis has weight 0; outside the crop it is not read.
+ *   blend     wx0 = 1 - ax, wy0 = 1 - ay,
+ *             out = wy0 * (wx0 * v00 + ax * v01) + ay * (wx0 * v10 + ax * v11),
+ *             every written operation rounded once (no contraction): raft_fb_consistency's order, so
+ *             |out_fp32 - out_exact| <= 10 * 2^-24 * max |tap|.
+ *   uint8     uint8 taps are widened to float first.  A uint8 output is the blend rounded to nearest
+ *             (ties to even) and saturated to 0..255 (NaN -> 0).
+ *
+ * Layout.  The flow is raft_fb_consistency's: float32 NCHW with unit element stride, element (b, c, y, x)
+ * of the frame at flow[b * batch_stride + c * chan_stride + (top + y) * pitch + left + x] (strides in
+ * floats), so a padded flow_up is read in place.  The frame is, by its dtype tag, either
+ * RAFT_FRAME_F32_NCHW: float32 with strides of its own and THE SAME crop offsets (top, left), any C >= 1,
+ * or RAFT_FRAME_U8_NHWC: uint8 [B][H][W][3], dense (strides and crop offsets are not read; C == 3).
+ * out is, by out_dtype, float32 [B][C][H][W] dense, 16-byte aligned, or uint8 [B][H][W][3] dense,
+ * 4-byte aligned (C == 3); all four combinations are supported.  valid is uint8 [B][H][W] (0 / 1),
+ * 4-byte aligned.  Nothing outside the crop is read.  out and valid alias neither each other nor an
+ * input.  B * H * W < 2^30. */
+#define RAFT_WARP_BORDER 1 /* clamp the sampling position to the frame (default: taps outside read 0) */
+int raft_warp_frame(const float* flow, long flow_batch_stride, long flow_chan_stride, long flow_pitch,
+                    const void* frame, int frame_dtype, long frame_batch_stride, long frame_chan_stride,
+                    long frame_pitch, int top, int left, int B, int C, int H, int W, int flags, void* out,
+                    int out_dtype, unsigned char* valid, raft_stream_t stream);
+
+/* Forward-warp density (UnFlow's forward_warp, Meister et al. 2018): how much of frame 1 lands on each
+ * pixel of frame 2 under the flow.  ~1 where the flow is a bijection, < 1 where nothing arrives (a
+ * disocclusion), > 1 where several sources pile up.
+ *
+ * Definition.  Source pixel (j, i) with d = flow(j, i), x0 / ax / y0 / ay as in raft_warp_frame,
+ * contributes iff dx and dy are finite, |d| < 2^30 on both axes, 0 <= x0 <= W-1 and 0 <= y0 <= H-1.
+ * With x1 = min(x0 + 1, W-1), y1 = min(y0 + 1, H-1), wx0 = 1 - ax, wy0 = 1 - ay it adds
+ *   wx0 * wy0 to (y0, x0),  ax * wy0 to (y0, x1),  wx0 * ay to (y1, x0),  ax * ay to (y1, x1)
+ * (on the last column / row both weights of the axis land on the edge pixel), each weight computed in
+ * fp32 with one rounding per operation.  density is the SUM of all contributions to a pixel.
+ *
+ * Accumulation.  Each weight w is quantised to unsigned 64-bit fixed point with unit 2^-32 by truncation
+ * (w * 2^32 is exact in fp32) and added with 64-bit integer atomics; a last pass converts every pixel's
+ * sum to float32 with one rounding.  Integer addition is associative: the result does not depend on the
+ * order the adds arrive in and is bitwise equal from run to run.  Three launches: zero, splat, convert.
+ * |density_fp32 - density_exact| <= n * (3 * 2^-24 + 2^-32) + 2^-24 * density for n contributing taps.
+ *
+ * Layout.  The flow as above.  ws: raft_splat_ws_bytes(B, H, W) bytes, 8-byte aligned (zeroed by the
+ * call itself); density float32 [B][H][W] dense.  density, ws and flow are distinct.  B * H * W < 2^30. */
+/* bytes of raft_splat_density's workspace; 0 for sizes it rejects */
+size_t raft_splat_ws_bytes(int B, int H, int W);
+int raft_splat_density(const float* flow, long batch_stride, long chan_stride, long pitch, int top, int left, int B,
+                       int H, int W, void* ws, float* density, raft_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

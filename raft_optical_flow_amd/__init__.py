@@ -7,8 +7,10 @@ and the alt_cuda_corr plugin module; the compute runs in libraft_hip.so
 """
 from .corr import AlternateCorrBlock, CorrBlock  # noqa: F401
 from .extractor import BasicEncoder, SmallEncoder  # noqa: F401
-from .raft import RAFT, BidirectionalFlow, BidirectionalFlowViz, FlowStream, FlowViz  # noqa: F401
+from .raft import (RAFT, BidirectionalFlow, BidirectionalFlowViz, BidirectionalFlowVizWarp,  # noqa: F401
+                   BidirectionalFlowWarp, FlowStream, FlowViz, FlowVizWarp, FlowWarp)
 from .update import BasicUpdateBlock, SmallUpdateBlock  # noqa: F401
-from .utils.utils import InputPadder, coords_grid, fb_consistency, ingest_frame, upflow8  # noqa: F401
+from .utils.utils import (InputPadder, coords_grid, fb_consistency, ingest_frame, splat_density,  # noqa: F401
+                          upflow8, warp_frame)
 
 __version__ = "0.1.0"

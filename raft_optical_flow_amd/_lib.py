@@ -40,6 +40,8 @@ VIZ_BGR = 1    # raft_flow_to_rgb flags: bytes in B, G, R order
 VIZ_UNIT = 2   # no normalisation (flow_uv_to_colors)
 VIZ_CLIP = 4   # clip both components to [0, clip_flow] first
 
+WARP_BORDER = 1   # raft_warp_frame flag: clamp the sampling position to the frame (default: zeros outside)
+
 EPI_LINEAR = 0
 EPI_RELU = 1
 EPI_RESID_RELU = 2
@@ -204,6 +206,10 @@ _PROTOS = {
     "raft_flow_viz_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "raft_flow_to_rgb": (c_int, [P, c_long, c_long, c_long, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_int,
                                  P, c_long, c_long, c_long, P, P, P]),
+    "raft_warp_frame": (c_int, [P, c_long, c_long, c_long, P, c_int, c_long, c_long, c_long, c_int, c_int, c_int,
+                                c_int, c_int, c_int, c_int, P, c_int, P, P]),
+    "raft_splat_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "raft_splat_density": (c_int, [P, c_long, c_long, c_long, c_int, c_int, c_int, c_int, c_int, P, P, P]),
 }
 
 EXPORTED = tuple(_PROTOS)

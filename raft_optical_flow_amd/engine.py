@@ -896,13 +896,17 @@ class StreamPlan:
       raft_init_coords ... raft_flow_from_coords, plan_refinement as RaftPlan's
       raft_flow_to_rgb    (visualize only) flow_up [B,2,Hp,Wp] in place (crop offsets = the padding) -> uint8
                           [B,H,W,3], with viz_stack under the pair's image1 (the `prev` raw frame)
+      raft_warp_frame     (warp only) flow_up and the `cur` raw frame, both in place (crop offsets = the padding)
+                          -> the current frame aligned with the previous one, in the pushed frame's layout, + valid
 
     The carry opens the step instead of closing it, so that after a step BOTH raw frames of its pair
     are still in the plan: the range guard's exact re-run and a rebuild after a weight change read
     them.  `prime()` (the first frame after a reset) is the short list ingest + fnet."""
 
     def __init__(self, pk: PackedRaft, B, H, W, iters, dtype_tag=_lib.FRAME_F32_NCHW, centred=True, alternate=False,
-                 warm_start=False, device=None, range_guard=True, visualize=None, viz_rad_max=None, viz_stack=False):
+                 warm_start=False, device=None, range_guard=True, visualize=None, viz_rad_max=None, viz_stack=False,
+                 warp=None):
+        self.warp = warp
         self.pk, self.B, self.H, self.W, self.iters = pk, B, H, W, iters
         self.dtype_tag, self.centred, self.alternate, self.warm_start = dtype_tag, bool(centred), alternate, warm_start
         self.visualize, self.viz_rad_max, self.viz_stack = visualize, viz_rad_max, bool(viz_stack)
@@ -964,6 +968,25 @@ class StreamPlan:
         L.append(K.JOIN)
         plan_refinement(self, L, pk, ub, B, Hp, Wp, iters, True, alternate, self.fmap_prev, device)
         self.rgb = [self._plan_viz(L, self.flow_up[0], self.raw_prev)] if self.visualize else None
+        # (tuples of one: the bidirectional plan holds one per direction)
+        self.warped, self.warp_valid = zip(self._plan_warp(L, self.flow_up[0], self.raw_cur)) if self.warp \
+            else (None, None)
+
+    def _plan_warp(self, L, up, frame):
+        """Append raft_warp_frame on B images: the raw padded `frame` [B,3,Hp,Wp] sampled at x + up(x), `up` the
+        padded flow [B,2,Hp,Wp]; both are read in place with the padding as crop offsets, so a target in the
+        padding is outside the frame.  Returns (warped, valid): warped in the pushed frame's own layout (uint8
+        [B,H,W,3] for uint8 frames, else float32 [B,3,H,W]), valid uint8 [B,1,H,W]."""
+        B, H, W, Hp, Wp = self.B, self.H, self.W, self.Hp, self.Wp
+        u8 = self.dtype_tag == _lib.FRAME_U8_NHWC
+        out = torch.zeros((B, H, W, 3) if u8 else (B, 3, H, W), dtype=torch.uint8 if u8 else torch.float32,
+                          device=up.device)
+        valid = torch.zeros(B, 1, H, W, dtype=torch.uint8, device=up.device)
+        L.append(Launch("raft_warp_frame", up.data_ptr(), 2 * Hp * Wp, Hp * Wp, Wp, frame.data_ptr(),
+                        _lib.FRAME_F32_NCHW, 3 * Hp * Wp, Hp * Wp, Wp, self.pad[2], self.pad[0], B, 3, H, W,
+                        _lib.WARP_BORDER if self.warp == "border" else 0, out.data_ptr(), self.dtype_tag,
+                        valid.data_ptr(), keep=(up, frame, out, valid)))
+        return out, valid
 
     def _plan_viz(self, L, up, frame):
         """Append raft_flow_to_rgb (its maximum launch, skipped with a fixed viz_rad_max, and its colour launch)
@@ -1041,7 +1064,8 @@ class StreamPlan:
         self.launches, self.prime_launches, self._fnet, self._ingest = [], [], [], None
         self.arena.bufs.clear()
         for name in ("pyramid", "corr_ws", "f2levels", "ub", "frame_in", "rows_prev", "rows_cur", "raw_prev", "raw_cur",
-                     "fmap_prev", "fmap_cur", "flow_init", "flow_low", "flow_up", "range_flag", "rgb"):
+                     "fmap_prev", "fmap_cur", "flow_init", "flow_low", "flow_up", "range_flag", "rgb", "warped",
+                     "warp_valid"):
             if hasattr(self, name):
                 setattr(self, name, None)
 
@@ -1084,6 +1108,8 @@ class BidiStreamPlan(StreamPlan):
       raft_init_coords ... raft_flow_from_coords, plan_refinement at batch 2B
       raft_fb_consistency  flow_up [2B,2,Hp,Wp] in place (crop offsets = the padding) -> occ, err
       raft_flow_to_rgb     (visualize only) once per direction
+      raft_warp_frame      (warp only) once per direction: the current frame by the forward flow, the previous
+                           frame by the backward flow
 
     `prime()` is ingest + fnet + cnet + the context terms of the first frame."""
 
@@ -1159,6 +1185,9 @@ class BidiStreamPlan(StreamPlan):
         # previous frame, backward: the current one), and each output has an aligned base of its own
         self.rgb = [self._plan_viz(L, up[:B], self.raw_prev), self._plan_viz(L, up[B:], self.raw_cur)] \
             if self.visualize else None
+        # forward: the current frame pulled back onto the previous one; backward: the previous onto the current
+        self.warped, self.warp_valid = zip(self._plan_warp(L, up[:B], self.raw_cur),
+                                           self._plan_warp(L, up[B:], self.raw_prev)) if self.warp else (None, None)
 
     def _state(self):
         P = self.B * self.h * self.w

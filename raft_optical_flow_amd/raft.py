@@ -62,7 +62,7 @@ from .engine import BidiStreamPlan, PackedRaft, RaftPlan, StreamPlan, frame_layo
 from .extractor import BasicEncoder, SmallEncoder
 from .update import BasicUpdateBlock, SmallUpdateBlock
 from .utils.flow_viz import check_viz_options, flow_to_rgb
-from .utils.utils import check_fb_params, coords_grid, fb_consistency
+from .utils.utils import check_fb_params, check_warp_option, coords_grid, fb_consistency, warp_frame
 
 # module attribute kept for API parity with core/raft.py:11-22 (callers monkeypatch it);
 # the HIP path never autocasts: its arithmetic is RAFT.conv_precision
@@ -356,16 +356,19 @@ class RAFT(nn.Module):
 
 
     def stream(self, iters=12, warm_start=False, pad_mode="sintel", bidirectional=False, fb_alpha=0.01, fb_beta=0.5,
-               visualize=None, viz_rad_max=None, viz_stack=False):
+               visualize=None, viz_rad_max=None, viz_stack=False, warp=None):
         """A FlowStream over consecutive video frames: `push(frame)` returns (flow_low, flow_up) of
         (previous frame, this frame), and every frame passes through the feature network once.
         bidirectional=True: push returns a BidirectionalFlow (both directions, their occlusion masks and
         forward-backward residuals; fb_alpha / fb_beta are the check's constants, utils.fb_consistency).
         visualize="rgb" / "bgr": the step also colours flow_up on the device (utils.flow_viz.flow_to_rgb) and
         push returns a FlowViz (or a BidirectionalFlowViz); viz_rad_max fixes the colour scale for the whole
-        video, viz_stack puts the pair's first frame above the colours as demo.py does."""
+        video, viz_stack puts the pair's first frame above the colours as demo.py does.
+        warp="zeros" / "border": the step also warps the current frame back onto the previous one by flow_up
+        (utils.warp_frame; bidirectional: both frames, each by its direction's flow) and push returns a FlowWarp
+        (or the matching tuple below) with `warped, valid` appended."""
         return FlowStream(self, iters, warm_start, pad_mode, bidirectional, fb_alpha, fb_beta, visualize, viz_rad_max,
-                          viz_stack)
+                          viz_stack, warp)
 
 
 _TRAINING_MSG = ("raft_optical_flow_amd.RAFT is an inference path: call model.eval() "
@@ -395,6 +398,26 @@ up_bw (FlowViz.rgb).  Each is normalised by its own maximum unless viz_rad_max i
 lies under the previous frame and rgb_bw under the current one (each direction's image1)."""
 
 
+FlowWarp = namedtuple("FlowWarp", ["flow_low", "flow_up", "warped", "valid"])
+FlowWarp.__doc__ = """What FlowStream.push returns with warp set: (flow_low, flow_up) as without it, then
+  warped  the current frame sampled at x + flow_up(x): aligned with the previous frame; in the pushed frame's own
+          layout (float32 [B,3,H,W], or uint8 [B,H,W,3] for uint8 frames)
+  valid   bool [B,1,H,W]: x + flow_up(x) lies in the frame (a target in the padding is outside)
+utils.warp_frame(current frame, flow_up, padding=warp) of the same step, computed inside the step."""
+
+FlowVizWarp = namedtuple("FlowVizWarp", FlowViz._fields + ("warped", "valid"))
+FlowVizWarp.__doc__ = """FlowViz's fields, then FlowWarp's warped and valid (visualize and warp both set)."""
+
+_BIDI_WARP = ("warped_fw", "warped_bw", "valid_fw", "valid_bw")
+BidirectionalFlowWarp = namedtuple("BidirectionalFlowWarp", BidirectionalFlow._fields + _BIDI_WARP)
+BidirectionalFlowWarp.__doc__ = """BidirectionalFlow's fields, then warped_fw: the current frame warped by up_fw
+(aligned with the previous frame), warped_bw: the previous frame warped by up_bw (aligned with the current one),
+and their in-frame masks valid_fw, valid_bw (FlowWarp.warped / valid)."""
+
+BidirectionalFlowVizWarp = namedtuple("BidirectionalFlowVizWarp", BidirectionalFlowViz._fields + _BIDI_WARP)
+BidirectionalFlowVizWarp.__doc__ = """BidirectionalFlowViz's fields, then BidirectionalFlowWarp's four."""
+
+
 class FlowStream:
     """Optical flow over a video, one frame per call (RAFT.stream).
 
@@ -410,6 +433,12 @@ class FlowStream:
     viz_rad_max=None normalises every image by its own maximum, as the reference's flow_to_image does; a positive
     number fixes the scale so that colours do not flicker from frame to frame.  viz_stack=True puts the pair's
     first frame above the colours ([B,2H,W,3], demo.py's layout).
+
+    warp="zeros" / "border": push returns a FlowWarp (flow_low, flow_up, warped, valid): the current frame
+    warped back onto the previous one by flow_up inside the step (utils.warp_frame of the same flow, bit for
+    bit), in the pushed frame's layout and dtype, and the mask of the targets that lie in the frame.  With
+    visualize the two fields follow rgb (FlowVizWarp); bidirectional streams append warped_fw, warped_bw,
+    valid_fw, valid_bw (BidirectionalFlowWarp / BidirectionalFlowVizWarp).
 
     bidirectional=True: push returns a BidirectionalFlow instead (both flows, occlusion masks, residuals);
     it equals model(cat[pad(prev), pad(cur)], cat[pad(cur), pad(prev)], iters, flow_init=s.last_flow_init,
@@ -429,8 +458,9 @@ class FlowStream:
     as "fallback", because the next step consumes this step's flow_low."""
 
     def __init__(self, model, iters=12, warm_start=False, pad_mode="sintel", bidirectional=False, fb_alpha=0.01,
-                 fb_beta=0.5, visualize=None, viz_rad_max=None, viz_stack=False):
+                 fb_beta=0.5, visualize=None, viz_rad_max=None, viz_stack=False, warp=None):
         self.visualize, self.viz_rad_max = check_viz_options(visualize, viz_rad_max)
+        self.warp = check_warp_option(warp)
         if not isinstance(viz_stack, bool):
             raise TypeError(f"viz_stack must be a bool, got {type(viz_stack).__name__}")
         self.viz_stack = viz_stack
@@ -501,7 +531,8 @@ class FlowStream:
         tag, b, h, w = self.layout
         kw = dict(dtype_tag=tag, centred=self.centred, alternate=bool(m.args.alternate_corr),
                   warm_start=self.warm_start, device=device, range_guard=m.range_guard != "off",
-                  visualize=self.visualize, viz_rad_max=self.viz_rad_max, viz_stack=self.viz_stack)
+                  visualize=self.visualize, viz_rad_max=self.viz_rad_max, viz_stack=self.viz_stack,
+                  warp=self.warp)
         if self.bidirectional:
             return BidiStreamPlan(pk, b, h, w, self.iters, fb_alpha=self.fb_alpha, fb_beta=self.fb_beta, **kw)
         return StreamPlan(pk, b, h, w, self.iters, **kw)
@@ -576,6 +607,8 @@ class FlowStream:
         if bidi:
             occ, err = [o.view(torch.bool).clone() for o in pl.occ], [e.clone() for e in pl.err]
         rgb = [t.clone() for t in pl.rgb] if self.visualize else None
+        if self.warp:
+            warped, wvalid = [t.clone() for t in pl.warped], [t.view(torch.bool).clone() for t in pl.warp_valid]
         mode = m.range_guard
         if pl.guarded and mode != "off":
             raised = bool(int(pl.range_flag.item()))
@@ -598,6 +631,11 @@ class FlowStream:
                     rgb = [flow_to_rgb(up[k * B:(k + 1) * B], self.viz_rad_max, None, self.visualize == "bgr",
                                        fr[crop] if self.viz_stack else None)
                            for k, fr in enumerate((pl.raw_prev, pl.raw_cur)[:2 if bidi else 1])]
+                if self.warp:  # the warps by the exact flows (forward: of the current frame)
+                    crop = (Ellipsis, slice(top, pl.Hp - bottom), slice(left, pl.Wp - right))
+                    ww = [warp_frame(fr[crop], up[k * B:(k + 1) * B], self.warp, pl.warped[0].dtype)
+                          for k, fr in enumerate((pl.raw_cur, pl.raw_prev)[:2 if bidi else 1])]
+                    warped, wvalid = [w[0] for w in ww], [w[1] for w in ww]
                 pl.flow_low.copy_(low)  # the next warm start begins from the exact flow
             # (a flagged step leaves this frame's feature map inexact: the next pair is re-run as well)
             self._inexact_prev = raised
@@ -605,7 +643,13 @@ class FlowStream:
             self._prev_low = low.clone()
         if bidi:
             out = BidirectionalFlow(low[:B], up[:B], low[B:], up[B:], occ[0], occ[1], err[0], err[1])
+            if self.warp:
+                return BidirectionalFlowVizWarp(*out, *rgb, *warped, *wvalid) if self.visualize else \
+                    BidirectionalFlowWarp(*out, *warped, *wvalid)
             return BidirectionalFlowViz(*out, *rgb) if self.visualize else out
+        if self.warp:
+            return FlowVizWarp(low, up, rgb[0], warped[0], wvalid[0]) if self.visualize else \
+                FlowWarp(low, up, warped[0], wvalid[0])
         return FlowViz(low, up, rgb[0]) if self.visualize else (low, up)
 
 

@@ -12,6 +12,15 @@
                                                    of one video frame in one launch (raft_ingest_frame)
   fb_consistency       (no reference counterpart)  forward-backward consistency of a flow pair: occlusion
                                                    masks and squared residuals (raft_fb_consistency)
+  warp_frame           unflow_loss_pytorch.py:27-80 backward warp of a frame by a flow, float32 or uint8, with
+                       IFNET_m.py:7-21              the in-frame mask (raft_warp_frame).  warp_frame(img, flow) is
+                       unflow_ops_pytorch.py:88     the reference's image_warp(img, flow) and its
+                                                   backward_warp_op(img, -flow); padding="border" is
+                                                   IFNET_m.warp(img, flow).  (The reference passes NHWC
+                                                   images and flows; here both are NCHW, or uint8 NHWC frames.)
+  splat_density        unflow_ops_pytorch.py:6-85   UnFlow's forward-warp density, every contribution summed
+                                                   (the reference's indexed `+=` keeps the last write only),
+                                                   bitwise reproducible (raft_splat_density)
 
 Every helper computes on the GPU through the HIP kernels of libraft_hip.so; a CPU tensor is
 copied to the current GPU and the result copied back (there is no host computation path).
@@ -227,3 +236,111 @@ def ingest_frame(frame, mode="sintel"):
     _lib().call("raft_ingest_frame", x.data_ptr(), tag, b, h, w, int(centred), rows.data_ptr(), padded.data_ptr(),
                 _stream())
     return rows, padded, pad
+
+
+def _check_flow(name, flow):
+    """(B, H, W) of a flow, float32 [B,2,H,W] with fewer than 2^30 pixels; raises otherwise."""
+    if not torch.is_tensor(flow):
+        raise TypeError(f"{name}: flow must be a tensor, got {type(flow).__name__}")
+    if flow.dtype != torch.float32:
+        raise TypeError(f"{name}: flow must be float32, got {flow.dtype}")
+    if flow.dim() != 4 or flow.shape[1] != 2 or flow.numel() == 0:
+        raise ValueError(f"{name}: flow must be [B, 2, H, W], got {tuple(flow.shape)}")
+    b, _, h, w = flow.shape
+    if b * h * w >= 1 << 30:
+        raise ValueError(f"{name}: {b} x {h} x {w} pixels exceed 2^30")
+    return b, h, w
+
+
+def _pitched(t, h, w):
+    """t [B,C,H,W] with unit element stride and a row pitch that holds a row, as (tensor, strides)."""
+    if t.stride(3) != 1 and w > 1 or (h > 1 and t.stride(2) < w):
+        t = t.contiguous()
+    return t, (t.stride(0), t.stride(1), t.stride(2) if h > 1 else w)
+
+
+WARP_PADDING = ("zeros", "border")
+
+
+def check_warp_option(warp):
+    """RAFT.stream's warp option: None, "zeros" or "border"."""
+    if warp is not None and warp not in WARP_PADDING:
+        raise ValueError(f'warp must be None, "zeros" or "border", got {warp!r}')
+    return warp
+
+
+def warp_frame(frame, flow, padding="zeros", out_dtype=None):
+    """Backward warp (raft_warp_frame, one launch): warped(x) = bilinear frame(x + flow(x)).
+
+    frame is float32 [B,C,H,W] (any C >= 1) or uint8 [B,H,W,3]; flow [B,2,H,W] float32 (channel 0 = x); GPU
+    tensors, crops of larger tensors are read in place.  With flow = the flow from frame 1 to frame 2 and
+    frame = frame 2, the result is frame 2 aligned with frame 1.  padding="zeros": taps outside the frame read
+    0 (grid_sample's zeros with align_corners=True: the reference's image_warp); "border": the position is
+    clamped to the frame (IFNET_m.warp).  A pixel whose flow is not finite (or >= 2^30) is 0.
+    Returns (warped, valid): warped in the frame's dtype and layout, or out_dtype's (torch.float32:
+    [B,C,H,W]; torch.uint8: [B,H,W,3], rounded to nearest even and saturated; C must be 3); valid bool
+    [B,1,H,W], True where x + flow(x) lies in [0, W-1] x [0, H-1].  include/raft_hip.h has the definition."""
+    L = _lib()
+    b, h, w = _check_flow("warp_frame", flow)
+    if not torch.is_tensor(frame):
+        raise TypeError(f"warp_frame: frame must be a tensor, got {type(frame).__name__}")
+    if frame.dtype not in (torch.float32, torch.uint8):
+        raise TypeError(f"warp_frame: frame must be float32 [B,C,H,W] or uint8 [B,H,W,3], got {frame.dtype}")
+    if padding not in WARP_PADDING:
+        raise ValueError(f'warp_frame: padding must be "zeros" or "border", got {padding!r}')
+    if out_dtype is None:
+        out_dtype = frame.dtype
+    if out_dtype not in (torch.float32, torch.uint8):
+        raise TypeError(f"warp_frame: out_dtype must be None, torch.float32 or torch.uint8, got {out_dtype!r}")
+    in_u8, out_u8 = frame.dtype == torch.uint8, out_dtype == torch.uint8
+    if frame.dim() != 4:
+        raise ValueError(f"warp_frame: frame must be float32 [B, C, H, W] or uint8 [B, H, W, 3], got "
+                         f"{tuple(frame.shape)}")
+    if in_u8:
+        if frame.shape[3] != 3:
+            raise ValueError(f"warp_frame: a uint8 frame is [B, H, W, 3], got {tuple(frame.shape)}")
+        fb, c, fh, fw = frame.shape[0], 3, frame.shape[1], frame.shape[2]
+    else:
+        fb, c, fh, fw = frame.shape
+    if (fb, fh, fw) != (b, h, w) or c < 1:
+        raise ValueError(f"warp_frame: frame {tuple(frame.shape)} and flow {tuple(flow.shape)} differ in size")
+    if out_u8 and c != 3:
+        raise ValueError(f"warp_frame: a uint8 result needs 3 channels, the frame has {c}")
+    for name, t in (("frame", frame), ("flow", flow)):
+        if not t.is_cuda:
+            raise RuntimeError(f"warp_frame runs on a ROCm GPU only: {name} is on {t.device} (no CPU path)")
+    if frame.device != flow.device:
+        raise RuntimeError(f"warp_frame: frame is on {frame.device}, flow on {flow.device}")
+    with torch.cuda.device(flow.device):
+        fl, sfl = _pitched(flow, h, w)
+        if in_u8:
+            fr, sfr = frame.contiguous(), (0, 0, 0)
+        else:
+            fr, sfr = _pitched(frame, h, w)
+        dev = flow.device
+        out = torch.empty((b, h, w, 3) if out_u8 else (b, c, h, w), dtype=out_dtype, device=dev)
+        valid = torch.empty(b, 1, h, w, dtype=torch.uint8, device=dev)
+        L.call("raft_warp_frame", fl.data_ptr(), *sfl, fr.data_ptr(), L.FRAME_U8_NHWC if in_u8 else L.FRAME_F32_NCHW,
+               *sfr, 0, 0, b, c, h, w, L.WARP_BORDER if padding == "border" else 0, out.data_ptr(),
+               L.FRAME_U8_NHWC if out_u8 else L.FRAME_F32_NCHW, valid.data_ptr(), _stream())
+    return out, valid.view(torch.bool)
+
+
+def splat_density(flow):
+    """UnFlow's forward-warp density (raft_splat_density): every pixel x splats its four bilinear weights at
+    x + flow(x); the result, float32 [B,1,H,W], is the sum of what lands on each pixel: ~1 where the flow is
+    one-to-one, below 1 where nothing arrives (a disocclusion), above 1 where sources pile up.  A source whose
+    flow is not finite, or whose target's floor lies outside the frame, contributes nothing; on the last
+    column / row both weights land on the edge pixel (the reference's clamp).  The sum is accumulated in
+    64-bit fixed point: it does not depend on the order of the adds and is bitwise equal from run to run.
+    flow [B,2,H,W] float32 on a GPU, any strides."""
+    L = _lib()
+    b, h, w = _check_flow("splat_density", flow)
+    if not flow.is_cuda:
+        raise RuntimeError(f"splat_density runs on a ROCm GPU only: flow is on {flow.device} (no CPU path)")
+    with torch.cuda.device(flow.device):
+        fl, sfl = _pitched(flow, h, w)
+        ws = torch.empty(L.load().raft_splat_ws_bytes(b, h, w) // 8, dtype=torch.int64, device=fl.device)
+        out = torch.empty(b, 1, h, w, device=fl.device)
+        L.call("raft_splat_density", fl.data_ptr(), *sfl, 0, 0, b, h, w, ws.data_ptr(), out.data_ptr(), _stream())
+    return out
