@@ -851,6 +851,13 @@ __global__ __launch_bounds__(256) void alt_corr_generic_kernel(AltArgs a, int ro
   }
 }
 
+// whether the MFMA tile kernel takes the lookup: a split precision, radius 4, whole 32-channel K-steps
+// (RAFT_ALT_MFMA=0: never)
+bool alt_mfma_applies(int prec, int r, int C) {
+  static const bool off = env_off("RAFT_ALT_MFMA");
+  return !off && prec != RAFT_PREC_FP32 && r == 4 && C % 32 == 0 && C <= 256;
+}
+
 int launch_alt(const AltArgs& a, raft_stream_t stream) {
   hipStream_t s = as_stream(stream);
   if (a.r > 4) {  // any radius: the generic kernel
@@ -860,11 +867,7 @@ int launch_alt(const AltArgs& a, raft_stream_t stream) {
                        (size_t)(4 * row * sizeof(float)), s, a, row);
     return check_launch("raft_alt_corr(generic radius)");
   }
-  static const bool mfma = [] {
-    const char* e = getenv("RAFT_ALT_MFMA");
-    return !(e && e[0] == '0');
-  }();
-  if (mfma && a.prec != RAFT_PREC_FP32 && a.r == 4 && a.C % 32 == 0 && a.C <= 256) {
+  if (alt_mfma_applies(a.prec, a.r, a.C)) {
     const long tiles = (long)a.B * a.N * cdiv_l(a.H1, AT) * cdiv_l(a.W1, AT);
     AltLevels lv{};
     lv.f2[0] = a.f2;
@@ -917,13 +920,6 @@ extern "C" int raft_debug_altstamps(unsigned long long* host, int n) {
 
 using namespace raft;
 
-static int grid_for(long n, int block = 256) {
-  long g = (n + block - 1) / block;
-  if (g > 65536) g = 65536;
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
 static int alt_checks(const float* f1, const float* f2, const float* coords, const float* out, int B, int H1, int W1,
                       int H2, int W2, int C, int N, int r) {
   RAFT_REQUIRE(f1 && f2 && coords && out, "raft_alt_corr: null pointer");
@@ -933,6 +929,35 @@ static int alt_checks(const float* f1, const float* f2, const float* coords, con
   RAFT_REQUIRE((((uintptr_t)f1 | (uintptr_t)f2) & 15) == 0, "raft_alt_corr: fmaps must be 16-byte aligned");
   RAFT_REQUIRE((long)H2 * W2 * C * 4 < (1L << 31), "raft_alt_corr: one fmap2 exceeds 2 GiB");
   return 0;
+}
+
+// the kernels' argument: one lookup of fmap1 (B x H1 x W1 x C) against N maps fmap2 (H2 x W2 x C)
+static AltArgs alt_args(const float* f1, const float* f2, const float* coords, int coords_layout, float coord_div,
+                        float* out, int out_layout, int out_ld, int B, int H1, int W1, int H2, int W2, int C, int N,
+                        int r, float scale_div, float* flow, int flow_ld, int* range_flag, int prec) {
+  AltArgs a;
+  a.f1 = f1;
+  a.f2 = f2;
+  a.coords = coords;
+  a.coords_layout = coords_layout;
+  a.coord_div = coord_div;
+  a.out = out;
+  a.out_layout = out_layout;
+  a.out_ld = out_ld;
+  a.B = B;
+  a.H1 = H1;
+  a.W1 = W1;
+  a.H2 = H2;
+  a.W2 = W2;
+  a.C = C;
+  a.N = N;
+  a.r = r;
+  a.scale_div = scale_div;
+  a.flow = flow;
+  a.flow_ld = flow_ld;
+  a.range_flag = range_flag;
+  a.prec = prec;
+  return a;
 }
 
 extern "C" int raft_alt_corr_forward(const float* fmap1, const float* fmap2, const float* coords, float* corr, int B,
@@ -948,29 +973,9 @@ extern "C" int raft_alt_corr_forward_prec(const float* fmap1, const float* fmap2
                                           float scale_div, int precision, raft_stream_t stream) {
   int rc = alt_checks(fmap1, fmap2, coords, corr, B, H1, W1, H2, W2, C, N, radius);
   if (rc) return rc;
-  AltArgs a;
-  a.f1 = fmap1;
-  a.f2 = fmap2;
-  a.coords = coords;
-  a.coords_layout = 0;
-  a.coord_div = 1.0f;
-  a.out = corr;
-  a.out_layout = 0;
-  a.out_ld = 0;
-  a.B = B;
-  a.H1 = H1;
-  a.W1 = W1;
-  a.H2 = H2;
-  a.W2 = W2;
-  a.C = C;
-  a.N = N;
-  a.r = radius;
-  a.scale_div = scale_div;
-  a.flow = nullptr;
-  a.flow_ld = 0;
-  a.range_flag = nullptr;
-  a.prec = precision;
-  return launch_alt(a, stream);
+  return launch_alt(alt_args(fmap1, fmap2, coords, 0, 1.0f, corr, 0, 0, B, H1, W1, H2, W2, C, N, radius, scale_div,
+                             nullptr, 0, nullptr, precision),
+                    stream);
 }
 
 extern "C" int raft_alt_corr_lookup_nhwc(const float* fmap1, const float* fmap2, const float* coords,
@@ -991,29 +996,9 @@ extern "C" int raft_alt_corr_lookup_nhwc_prec(const float* fmap1, const float* f
   RAFT_REQUIRE(coords_layout == 0 || coords_layout == 1, "raft_alt_corr_lookup_nhwc: bad coords_layout");
   RAFT_REQUIRE(coord_div > 0.f, "raft_alt_corr_lookup_nhwc: coord_div must be > 0");
   RAFT_REQUIRE(out_ld >= (2 * radius + 1) * (2 * radius + 1), "raft_alt_corr_lookup_nhwc: out_ld too small");
-  AltArgs a;
-  a.f1 = fmap1;
-  a.f2 = fmap2;
-  a.coords = coords;
-  a.coords_layout = coords_layout;
-  a.coord_div = coord_div;
-  a.out = out;
-  a.out_layout = 1;
-  a.out_ld = out_ld;
-  a.B = B;
-  a.H1 = H1;
-  a.W1 = W1;
-  a.H2 = H2;
-  a.W2 = W2;
-  a.C = C;
-  a.N = 1;
-  a.r = radius;
-  a.scale_div = scale_div;
-  a.flow = flow_out;
-  a.flow_ld = flow_ld;
-  a.range_flag = range_flag;
-  a.prec = precision;
-  return launch_alt(a, stream);
+  return launch_alt(alt_args(fmap1, fmap2, coords, coords_layout, coord_div, out, 1, out_ld, B, H1, W1, H2, W2, C, 1,
+                             radius, scale_div, flow_out, flow_ld, range_flag, precision),
+                    stream);
 }
 
 extern "C" int raft_alt_corr_lookup_levels(const float* fmap1, const float* const* fmap2_levels, const int* h2s,
@@ -1039,11 +1024,7 @@ extern "C" int raft_alt_corr_lookup_levels_prec(const float* fmap1, const float*
     if (rc) return rc;
   }
   RAFT_REQUIRE(coords_layout == 0 || coords_layout == 1, "raft_alt_corr_lookup_levels: bad coords_layout");
-  static const bool mfma = [] {
-    const char* e = getenv("RAFT_ALT_MFMA");
-    return !(e && e[0] == '0');
-  }();
-  if (!(mfma && precision != RAFT_PREC_FP32 && radius == 4 && C % 32 == 0 && C <= 256)) {
+  if (!alt_mfma_applies(precision, radius, C)) {
     // one launch per level (raft_alt_corr_lookup_nhwc_prec; the flow is written with level 0)
     for (int l = 0; l < L; ++l) {
       int rc = raft_alt_corr_lookup_nhwc_prec(fmap1, fmap2_levels[l], coords, coords_layout, (float)(1 << l),
@@ -1054,28 +1035,8 @@ extern "C" int raft_alt_corr_lookup_levels_prec(const float* fmap1, const float*
     }
     return 0;
   }
-  AltArgs a;
-  a.f1 = fmap1;
-  a.f2 = fmap2_levels[0];
-  a.coords = coords;
-  a.coords_layout = coords_layout;
-  a.coord_div = 1.f;
-  a.out = out;
-  a.out_layout = 1;
-  a.out_ld = out_ld;
-  a.B = B;
-  a.H1 = H1;
-  a.W1 = W1;
-  a.H2 = h2s[0];
-  a.W2 = w2s[0];
-  a.C = C;
-  a.N = 1;
-  a.r = radius;
-  a.scale_div = scale_div;
-  a.flow = flow_out;
-  a.flow_ld = flow_ld;
-  a.range_flag = range_flag;
-  a.prec = precision;
+  const AltArgs a = alt_args(fmap1, fmap2_levels[0], coords, coords_layout, 1.f, out, 1, out_ld, B, H1, W1, h2s[0],
+                             w2s[0], C, 1, radius, scale_div, flow_out, flow_ld, range_flag, precision);
   AltLevels lv{};
   for (int l = 0; l < L; ++l) {
     lv.f2[l] = fmap2_levels[l];

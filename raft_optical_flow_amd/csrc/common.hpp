@@ -3,8 +3,10 @@
 
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 
 #include "raft_hip.h"
@@ -39,6 +41,50 @@ inline hipStream_t as_stream(raft_stream_t s) { return reinterpret_cast<hipStrea
 __host__ __device__ inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 __host__ __device__ inline int round_up(int a, int b) { return cdiv(a, b) * b; }
 __host__ __device__ inline long cdiv_l(long a, long b) { return (a + b - 1) / b; }
+
+// Tuning knobs from the environment (DESIGN.md lists them).  How often a knob is read shows where it is read:
+//   static const bool off = env_off("RAFT_X");   once, for the life of the process
+//   if (env_off("RAFT_X")) ...                   on every call (a test can switch it between launches)
+// env_off: the value starts with '0' (a default-on knob turned off); env_on: with '1' (an opt-in knob turned on).
+inline bool env_off(const char* name) {
+  const char* e = getenv(name);
+  return e && e[0] == '0';
+}
+inline bool env_on(const char* name) {
+  const char* e = getenv(name);
+  return e && e[0] == '1';
+}
+inline long env_long(const char* name, long dflt) {
+  const char* e = getenv(name);
+  return e ? atol(e) : dflt;
+}
+inline double env_double(const char* name, double dflt) {
+  const char* e = getenv(name);
+  return e ? atof(e) : dflt;
+}
+
+// work-groups of 256 threads for a grid-stride loop over n elements
+inline int grid_for(long n) {
+  const long g = (n + 255) / 256;
+  return (int)(g > 65536 ? 65536 : g < 1 ? 1 : g);
+}
+
+// The CU count of the current device, cached per device (a process may drive several GPUs); 256, MI355X's,
+// where there is none to ask.
+inline long device_cus() {
+  constexpr int MAXDEV = 64;
+  static std::atomic<int> cache[MAXDEV];  // 0 = not queried yet
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return 256L;
+  if (dev >= 0 && dev < MAXDEV) {
+    const int c = cache[dev].load(std::memory_order_relaxed);
+    if (c > 0) return (long)c;
+  }
+  int cus = 0;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+  if (dev >= 0 && dev < MAXDEV) cache[dev].store(cus, std::memory_order_relaxed);
+  return (long)cus;
+}
 
 // XCD-aware tile order.  The dispatcher deals work-groups round-robin over the
 // 8 XCDs (work-group L -> XCD L % 8), each with its own L2; hand XCD c a

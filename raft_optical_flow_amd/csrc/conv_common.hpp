@@ -389,7 +389,23 @@ struct HaloOperands {
 // (the C header gives the struct and its query function one name: the type needs its tag keyword)
 using ConvForm = struct raft_conv2d_form;
 
-// conv_halo.hip: the halo-tiled LDS-DMA kernel for stride-1 "same" convs;
+// What the host decides about a conv's launch on the halo kernel, beside its operands (conv_halo.hip:
+// halo_plan decides all of it in one place; the launch and every query read these fields)
+struct HaloForm {
+  int th, bn;       // tile rows (8, or 16: the big tiles) and tile columns (32, 64 or 128)
+  bool enc;         // the instantiation with the encoder features (stats_part / in_norm)
+  int nl, ks;       // loader waves (4 or 8), compute waves per SIMD (1 or 2)
+  bool mt;          // the multi-tile body
+  int m;            // spatial tiles per work-group
+  long wgs;         // work-groups
+  int stats_slots;  // tile-statistics slots per image that instantiation writes (raft_conv2d_stats_slots)
+  bool norm_ok;     // the conv can take its input InstanceNorm in the loaders (raft_conv2d_in_norm_ok)
+};
+
+// conv_halo.hip: the halo-tiled LDS-DMA kernel for stride-1 "same" convs.
+// The plan of the conv's launch; false when the conv is not one the kernel covers.  enc: plan it as
+// with stats_part / in_norm set (the planner asks the queries before it sets them).
+bool conv_halo_plan(const HaloOperands& o, bool enc, HaloForm& f);
 // returns 1 (nothing launched) when the conv is not one it covers
 // (all three: with form != nullptr the call is raft_conv2d_form's query -- the same decisions, the form
 // of the launch written to *form (the pair: form[0] and form[1]) and nothing launched)
@@ -398,13 +414,7 @@ int conv_halo_launch(const HaloOperands& o, hipStream_t s, ConvForm* form = null
 int conv_halo_launch_pair(const HaloOperands& o0, const HaloOperands& o1, hipStream_t s, ConvForm* form = nullptr);
 // conv_stem.hip: the encoders' 7x7 / stride-2 stem over 3 channels; 1 (nothing launched) otherwise
 int conv_stem_launch(const raft_conv2d_params& p, int k_pad, hipStream_t s, ConvForm* form = nullptr);
-// tile-statistics slots per image of a conv on the halo / stem kernel (raft_conv2d_stats_slots), 0 if none
-int conv_halo_stats_slots(const HaloOperands& o);
-// whether conv_halo_launch takes the conv
-bool conv_halo_covers(const HaloOperands& o);
-int conv_halo_tile_rows(const HaloOperands& o);
-int conv_halo_tiles_per_wg(const HaloOperands& o);
-bool conv_halo_norm_ok(const HaloOperands& o);
+// tile-statistics slots per image of a conv on the stem kernel (raft_conv2d_stats_slots), 0 if none
 int conv_stem_stats_slots(const raft_conv2d_params& p, int k_pad);
 
 }  // namespace raft

@@ -932,10 +932,7 @@ int conv_dispatch(const raft_conv2d_params* pp, raft_stream_t stream, ConvForm* 
         p.pad_w == 1 && p.out_h == p.in_h && p.out_w == p.in_w) {
       // 4x16 tiles while they fill the CUs; 2x16 (twice the work-groups) when not
       const long t4 = (long)p.batch * cdiv(p.out_h, 4) * cdiv(p.out_w, 16);
-      static const long th4_min = [] {
-        const char* e = getenv("RAFT_SN_TH4_MIN");
-        return e ? atol(e) : (long)SN_TH4_MIN_TILES;
-      }();
+      static const long th4_min = env_long("RAFT_SN_TH4_MIN", SN_TH4_MIN_TILES);
       const int sn_th = t4 >= th4_min ? 4 : 2;
       if (q) {
         *q = ConvForm{};
@@ -1004,27 +1001,30 @@ extern "C" int raft_conv2d_form(const raft_conv2d_params* pp, ConvForm* out) {
   return rc;
 }
 
-extern "C" int raft_conv2d_in_norm_ok(const raft_conv2d_params* pp) {
+namespace {
+// the halo plan of a valid conv that raft_conv2d would offer to the halo kernel; false where there is none
+// (enc: conv_halo_plan)
+bool halo_query(const raft_conv2d_params* pp, bool enc, HaloForm& f) {
   ConvArgs a;
   HaloOperands o;
-  if (!pp || conv_prepare(pp, a, o)) return 0;
-  return pp->mode == RAFT_CONV_VEC && pp->n > 4 && conv_halo_norm_ok(o) ? 1 : 0;
+  if (!pp || conv_prepare(pp, a, o)) return false;
+  return pp->mode == RAFT_CONV_VEC && !small_n(*pp) && conv_halo_plan(o, enc, f);
+}
+}  // namespace
+
+extern "C" int raft_conv2d_in_norm_ok(const raft_conv2d_params* pp) {
+  HaloForm f;
+  return halo_query(pp, true, f) && f.norm_ok ? 1 : 0;
 }
 
 extern "C" int raft_conv2d_halo_tile_rows(const raft_conv2d_params* pp) {
-  ConvArgs a;
-  HaloOperands o;
-  if (!pp || conv_prepare(pp, a, o)) return 0;
-  if (pp->mode != RAFT_CONV_VEC || small_n(*pp)) return 0;
-  return conv_halo_tile_rows(o);
+  HaloForm f;
+  return halo_query(pp, false, f) ? f.th : 0;
 }
 
 extern "C" int raft_conv2d_halo_tiles_per_wg(const raft_conv2d_params* pp) {
-  ConvArgs a;
-  HaloOperands o;
-  if (!pp || conv_prepare(pp, a, o)) return 0;
-  if (pp->mode != RAFT_CONV_VEC || small_n(*pp)) return 0;
-  return conv_halo_tiles_per_wg(o);
+  HaloForm f;
+  return halo_query(pp, false, f) ? f.m : 0;
 }
 
 extern "C" int raft_conv2d_stats_slots(const raft_conv2d_params* pp) {
@@ -1034,15 +1034,12 @@ extern "C" int raft_conv2d_stats_slots(const raft_conv2d_params* pp) {
   const raft_conv2d_params& p = *pp;
   if (p.epilogue != RAFT_EPI_LINEAR || p.alpha != 1.0f || p.add0 || (p.n <= 4 && p.mode == RAFT_CONV_VEC)) return 0;
   if (p.mode == RAFT_CONV_VEC) {
-    const int hs = conv_halo_stats_slots(o);
-    if (hs > 0 || conv_halo_covers(o)) return hs;
+    HaloForm f;
+    if (conv_halo_plan(o, true, f)) return f.stats_slots;
     // the 64x64-tile GEMM (strided convs): two 32-row slots per tile of one image's rows
     // (RAFT_GEMM_STATS=0: none, the separate statistics pass)
-    static const bool on = [] {
-      const char* e = getenv("RAFT_GEMM_STATS");
-      return !(e && e[0] == '0');
-    }();
-    return on ? 2 * cdiv(p.out_h * p.out_w, BM) : 0;
+    static const bool off = env_off("RAFT_GEMM_STATS");
+    return off ? 0 : 2 * cdiv(p.out_h * p.out_w, BM);
   }
   return conv_stem_stats_slots(p, o.k_pad);
 }

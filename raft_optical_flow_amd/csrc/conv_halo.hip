@@ -1075,17 +1075,21 @@ __global__ __launch_bounds__(64 * (4 * KS + NL)) void conv_halo_kernel(HaloLaunc
   }
 }
 
-// the kernel of a launch: the multi-tile body where the plan runs several tiles per work-group
-// (l.m > 1), else the one-tile body.  (The one-product 3x3 wide tiles never run several:
-// halo_mt_ok.)
+// Everything the host decides about one halo launch: the kernel's argument and the instantiation that
+// takes it.  halo_plan (below) fills it, once, for a single conv and for a pair; launch_halo maps it to
+// the instantiation and the queries of raft_hip.h read its fields, so none of them decides anything.
+struct HaloPlan {
+  HaloLaunch l;
+  HaloForm f;
+};
+
 // the one-tile f16x3 update convs' loader waves: 8, or 4 (RAFT_HALO_NL8=0; raft_conv2d_set_halo_loaders)
 std::atomic<int> g_halo_nl{0};  // 0: from the environment
 bool halo_nl8() {
   int v = g_halo_nl.load(std::memory_order_relaxed);
   if (v == 0) {
     // (default 8: config 2 +1.0-1.4 % in three interleaved pairs on one box, profiles/r05e_experiments.txt)
-    const char* e = getenv("RAFT_HALO_NL8");
-    v = e && e[0] == '0' ? 4 : 8;
+    v = env_off("RAFT_HALO_NL8") ? 4 : 8;
     g_halo_nl.store(v, std::memory_order_relaxed);
   }
   return v == 8;
@@ -1098,8 +1102,7 @@ std::atomic<int> g_halo_ks{0};  // 0: from the environment
 bool halo_ks2() {
   int v = g_halo_ks.load(std::memory_order_relaxed);
   if (v == 0) {
-    const char* e = getenv("RAFT_HALO_KS2");
-    v = e && e[0] == '0' ? 1 : 2;
+    v = env_off("RAFT_HALO_KS2") ? 1 : 2;
     g_halo_ks.store(v, std::memory_order_relaxed);
   }
   return v == 2;
@@ -1107,131 +1110,163 @@ bool halo_ks2() {
 bool halo_nl8_enc() {
   // (default on: config 2 +0.1 / +0.3 % in two interleaved pairs on one box, profiles/r05f_experiments.txt;
   // read per launch so that a test can switch it -- a plan captures the launches it made)
-  const char* e = getenv("RAFT_HALO_NL8_ENC");
-  return !(e && e[0] == '0');
+  return !env_off("RAFT_HALO_NL8_ENC");
 }
-// the shapes compiled without the multi-tile body (launch_halo_mt): halo_mt_ok never plans m > 1 for
-// them, and the launch refuses m > 1 (the one-tile kernel would run only 1/m of the spatial tiles)
-constexpr bool halo_no_mt(int prec, int taps, int bn) { return prec != RAFT_PREC_F16X3 && taps == 9 && bn == 128; }
 
-// The last step of every halo launch: starts the chosen instantiation, or (the form query,
-// raft_conv2d_form: q != nullptr) writes its description to *q and starts nothing.  The launch and the
-// query run the same launch_halo* code down to this call, so what the query reports is what a launch runs.
+// Which instantiations exist beside <4 loader waves, 1 compute wave per SIMD, one tile> for a conv of
+// (prec, enc, th, bn, kh x kw).  halo_plan asks them at run time and launch_halo_mt at compile time, so
+// a plan never names an instantiation that is not compiled.
+// The shapes compiled without the multi-tile body: halo_mt_ok never plans m > 1 for them, and the launch
+// refuses m > 1 (the one-tile kernel would run only 1/m of the spatial tiles)
+constexpr bool halo_no_mt(int prec, int taps, int bn) { return prec != RAFT_PREC_F16X3 && taps == 9 && bn == 128; }
+// the 8-loader form: one-tile f16x3 update-block convs (default; RAFT_HALO_NL8=0: 4 loaders)
+constexpr bool halo_can_nl8(int prec, bool enc, int th, int bn, int kh, int kw) {
+  return prec == RAFT_PREC_F16X3 && !enc && th == HTH && bn <= 64 && kh * kw > 1;
+}
+// and for the encoders' f16x3 3x3 convs on 128-pixel tiles (default; RAFT_HALO_NL8_ENC=0: 4): their loaders
+// also apply the input InstanceNorm
+constexpr bool halo_can_nl8e(int prec, bool enc, int th, int bn, int kh, int kw) {
+  return prec == RAFT_PREC_F16X3 && enc && th == HTH && bn <= 64 && kh * kw == 9;
+}
+// the K-split form: the one-tile f16x3 update convs with 64-column tiles on the pre-split path (D = 3;
+// with 32-column tiles it was slower: profiles/r06b_experiments.txt)
+constexpr bool halo_can_ks2(int prec, bool enc, int th, int bn, int kh, int kw) {
+  return halo_can_nl8(prec, enc, th, bn, kh, kw) && bn == 64 &&
+         (kh == 3 ? HaloCfg<3, 3, 64>::D : kh == 1 ? HaloCfg<1, 5, 64>::D : HaloCfg<5, 1, 64>::D) == 3;
+}
+// LDS left for the input-norm tables of the 3x3 ENC instantiation on th x bn tiles (halo_norm_bytes)
+template <int BNT, int WR, int TH>
+constexpr long halo_norm_cap_t() {
+  using C = HaloCfg<3, 3, BNT, WR, TH>;
+  return halo_norm_bytes<3, 3, BNT, RAFT_PREC_F16X3, true>(C::LDS_B, C::LDS_A, C::D);
+}
+constexpr long halo_norm_cap(int bn, int prec, int th) {
+  const bool x3 = prec == RAFT_PREC_F16X3;
+  if (th == HTH_BIG) return x3 ? halo_norm_cap_t<64, 128, HTH_BIG>() : halo_norm_cap_t<64, 64, HTH_BIG>();
+  if (bn == 64) return x3 ? halo_norm_cap_t<64, 128, HTH>() : halo_norm_cap_t<64, 64, HTH>();
+  return x3 ? halo_norm_cap_t<32, 128, HTH>() : halo_norm_cap_t<32, 64, HTH>();
+}
+
+[[noreturn]] void halo_plan_error(const char* what, int v) {
+  fprintf(stderr, "raft_hip: internal error: %s (%d)\n", what, v);
+  abort();
+}
+
+// The last step of every halo launch: starts the instantiation the plan names (anything else is a
+// defect of launch_halo*, not of the caller).
 template <int KH, int KW, int BNT, int PREC, bool ENC, int TH, bool MT, int NL = 4, int KS = 1>
-void halo_start(const HaloLaunch& l, dim3 grid, hipStream_t s, ConvForm* q) {
-  if (q) {
-    *q = ConvForm{};
-    q->kernel = RAFT_CONV_KERNEL_HALO;
-    q->tile_rows = TH;
-    q->tile_cols = BNT;
-    q->tiles_per_wg = MT ? l.m : 1;
-    q->loader_waves = NL;
-    q->compute_waves_per_simd = KS;
-    return;
-  }
-  hipLaunchKernelGGL((conv_halo_kernel<KH, KW, BNT, PREC, ENC, TH, MT, NL, KS>), grid, dim3(64 * (4 * KS + NL)), 0, s, l);
+void halo_start(const HaloPlan& pl, hipStream_t s) {
+  const HaloForm& f = pl.f;
+  if (f.th != TH || f.bn != BNT || f.enc != ENC || f.mt != MT || f.nl != NL || f.ks != KS)
+    halo_plan_error("a halo plan reached another instantiation than it names, tile columns", BNT);
+  hipLaunchKernelGGL((conv_halo_kernel<KH, KW, BNT, PREC, ENC, TH, MT, NL, KS>), dim3((unsigned)f.wgs),
+                     dim3(64 * (4 * KS + NL)), 0, s, pl.l);
 }
 
 template <int KH, int KW, int BNT, int PREC, bool ENC = false, int TH = HTH>
-void launch_halo_mt(const HaloLaunch& l, dim3 grid, hipStream_t s, ConvForm* q) {
+void launch_halo_mt(const HaloPlan& pl, hipStream_t s) {
+  const HaloForm& f = pl.f;
   constexpr bool NO_MT = halo_no_mt(PREC, KH * KW, BNT);
-  if (NO_MT && l.m > 1) {
-    fprintf(stderr, "raft_hip: internal error: a one-tile-only halo conv was planned with %d tiles per work-group\n", l.m);
-    abort();
+  if (NO_MT && pl.l.m > 1)
+    halo_plan_error("a one-tile-only halo conv was planned with several tiles per work-group", pl.l.m);
+  if constexpr (ENC && KH == 3 && KW == 3) {  // halo_mt_ok fits the norm tables into this instantiation's LDS
+    using C = HaloCfg<KH, KW, BNT, PREC == RAFT_PREC_F16X3 ? 128 : 64, TH>;
+    static_assert(halo_norm_cap(BNT, PREC, TH) == halo_norm_bytes<KH, KW, BNT, PREC, ENC>(C::LDS_B, C::LDS_A, C::D));
   }
-  // the 8-loader form: one-tile f16x3 update-block convs (default; RAFT_HALO_NL8=0: 4 loaders)
-  constexpr bool CAN_NL8 = PREC == RAFT_PREC_F16X3 && !ENC && TH == HTH && BNT <= 64 && KH * KW > 1;
-  // and for the encoders' f16x3 3x3 convs on 128-pixel tiles (default; RAFT_HALO_NL8_ENC=0: 4): their loaders also
-  // apply the input InstanceNorm
-  constexpr bool CAN_NL8E = PREC == RAFT_PREC_F16X3 && ENC && TH == HTH && BNT <= 64 && KH * KW == 9;
-  if constexpr (CAN_NL8E) {
-    if (halo_nl8_enc()) {
-      if (l.m > 1)
-        halo_start<KH, KW, BNT, PREC, ENC, TH, true, 8>(l, grid, s, q);
+  if constexpr (halo_can_nl8e(PREC, ENC, TH, BNT, KH, KW)) {
+    if (f.nl == 8) {
+      if (f.mt)
+        halo_start<KH, KW, BNT, PREC, ENC, TH, true, 8>(pl, s);
       else
-        halo_start<KH, KW, BNT, PREC, ENC, TH, false, 8>(l, grid, s, q);
+        halo_start<KH, KW, BNT, PREC, ENC, TH, false, 8>(pl, s);
       return;
     }
   }
-  // the K-split form: the one-tile f16x3 update convs with 64-column tiles on the pre-split path
-  // (with 32-column tiles it was slower: profiles/r06b_experiments.txt)
-  constexpr bool CAN_KS2 = CAN_NL8 && BNT == 64 && HaloCfg<KH, KW, BNT, 128, TH>::D == 3;
-  if (!NO_MT && l.m > 1) {
-    halo_start<KH, KW, BNT, PREC, ENC, TH, !NO_MT>(l, grid, s, q);
+  if (!NO_MT && f.mt) {
+    halo_start<KH, KW, BNT, PREC, ENC, TH, !NO_MT>(pl, s);
   } else {
-    if constexpr (CAN_KS2) {
-      if (halo_ks2()) {
-        halo_start<KH, KW, BNT, PREC, ENC, TH, false, 4, 2>(l, grid, s, q);
+    if constexpr (halo_can_ks2(PREC, ENC, TH, BNT, KH, KW)) {
+      if (f.ks == 2) {
+        halo_start<KH, KW, BNT, PREC, ENC, TH, false, 4, 2>(pl, s);
         return;
       }
     }
-    if constexpr (CAN_NL8) {
-      if (halo_nl8()) {
-        halo_start<KH, KW, BNT, PREC, ENC, TH, false, 8>(l, grid, s, q);
+    if constexpr (halo_can_nl8(PREC, ENC, TH, BNT, KH, KW)) {
+      if (f.nl == 8) {
+        halo_start<KH, KW, BNT, PREC, ENC, TH, false, 8>(pl, s);
         return;
       }
     }
-    halo_start<KH, KW, BNT, PREC, ENC, TH, false>(l, grid, s, q);
+    halo_start<KH, KW, BNT, PREC, ENC, TH, false>(pl, s);
   }
 }
 
 template <int KH, int KW, int PREC>
-void launch_halo_p(const HaloLaunch& l, int bn, int th, dim3 grid, hipStream_t s, ConvForm* q) {
-  const raft_conv2d_params& p = l.a[0].p;
+void launch_halo_p(const HaloPlan& pl, hipStream_t s) {
+  const HaloForm& f = pl.f;
   if constexpr (KH == 3 && KW == 3) {
-    if (th == HTH_BIG) {  // (halo_pick: N tile 64)
-      if (p.stats_part || p.in_norm)
-        launch_halo_mt<3, 3, 64, PREC, true, HTH_BIG>(l, grid, s, q);
+    if (f.th == HTH_BIG) {
+      if (f.enc)
+        launch_halo_mt<3, 3, 64, PREC, true, HTH_BIG>(pl, s);
       else
-        launch_halo_mt<3, 3, 64, PREC, false, HTH_BIG>(l, grid, s, q);
+        launch_halo_mt<3, 3, 64, PREC, false, HTH_BIG>(pl, s);
       return;
     }
   } else if constexpr (KH * KW == 5) {
     // 1x5 / 5x1 big tiles: the one-product modes' 64-B weight rows leave LDS for the three pre-split
     // 16 x 20 patches the T = 5 ring needs (D = 3); f16x3's 128-B rows do not, so it runs D = 2 with
     // fp32 patches split by the compute waves (216 / 232 VGPRs)
-    if (th == HTH_BIG) {
-      launch_halo_mt<KH, KW, 64, PREC, false, HTH_BIG>(l, grid, s, q);
+    if (f.th == HTH_BIG) {
+      launch_halo_mt<KH, KW, 64, PREC, false, HTH_BIG>(pl, s);
       return;
     }
   }
   if constexpr (PREC != RAFT_PREC_F16X3) {
-    if (bn == 128) {  // (conv_halo_launch picks it only without stats_part / in_norm)
-      launch_halo_mt<KH, KW, 128, PREC>(l, grid, s, q);
+    if (f.bn == 128) {
+      launch_halo_mt<KH, KW, 128, PREC>(pl, s);
       return;
     }
   }
   if constexpr ((KH == 1 && KW == 1) || (KH == 3 && KW == 3)) {
-    if (p.stats_part || p.in_norm) {  // (one conv per launch: raft_conv2d_pair takes neither)
-      if (bn == 64)
-        launch_halo_mt<KH, KW, 64, PREC, true>(l, grid, s, q);
+    if (f.enc) {
+      if (f.bn == 64)
+        launch_halo_mt<KH, KW, 64, PREC, true>(pl, s);
       else
-        launch_halo_mt<KH, KW, 32, PREC, true>(l, grid, s, q);
+        launch_halo_mt<KH, KW, 32, PREC, true>(pl, s);
       return;
     }
   }
-  if (bn == 64)
-    launch_halo_mt<KH, KW, 64, PREC>(l, grid, s, q);
+  if (f.bn == 64)
+    launch_halo_mt<KH, KW, 64, PREC>(pl, s);
   else
-    launch_halo_mt<KH, KW, 32, PREC>(l, grid, s, q);
+    launch_halo_mt<KH, KW, 32, PREC>(pl, s);
 }
 template <int KH, int KW>
-void launch_halo_k(const HaloLaunch& l, int bn, int th, dim3 grid, hipStream_t s, ConvForm* q) {
-  const int prec = l.a[0].p.precision;
+void launch_halo_k(const HaloPlan& pl, hipStream_t s) {
+  const int prec = pl.l.a[0].p.precision;
   if (prec == RAFT_PREC_F16X3)
-    launch_halo_p<KH, KW, RAFT_PREC_F16X3>(l, bn, th, grid, s, q);
+    launch_halo_p<KH, KW, RAFT_PREC_F16X3>(pl, s);
   else if (prec == RAFT_PREC_BF16)
-    launch_halo_p<KH, KW, RAFT_PREC_BF16>(l, bn, th, grid, s, q);
+    launch_halo_p<KH, KW, RAFT_PREC_BF16>(pl, s);
   else
-    launch_halo_p<KH, KW, RAFT_PREC_F16>(l, bn, th, grid, s, q);
+    launch_halo_p<KH, KW, RAFT_PREC_F16>(pl, s);
+}
+// starts the instantiation the plan names
+void launch_halo(const HaloPlan& pl, hipStream_t s) {
+  const raft_conv2d_params& p = pl.l.a[0].p;
+  if (p.kh == 1 && p.kw == 1)
+    launch_halo_k<1, 1>(pl, s);
+  else if (p.kh == 3)
+    launch_halo_k<3, 3>(pl, s);
+  else if (p.kh == 1)
+    launch_halo_k<1, 5>(pl, s);
+  else
+    launch_halo_k<5, 1>(pl, s);
 }
 
 bool halo_enabled() {
-  static const bool enabled = [] {
-    const char* e = getenv("RAFT_CONV_HALO");
-    return !(e && e[0] == '0');
-  }();
-  return enabled;
+  static const bool off = env_off("RAFT_CONV_HALO");
+  return !off;
 }
 
 // The halo kernel's view of a conv it covers (stride 1, "same" padding, 1x1 / 3x3 / 1x5 /
@@ -1270,34 +1305,12 @@ long halo_spatial(const HaloArgs& a) { return (long)a.p.batch * a.tx_n * a.ty_n;
 // slower as big tiles).  RAFT_HALO_BIG_MIN=0 turns them off (default 1: no other floor).
 // f16x3 needs the scaled weight (raft_conv2d_params.weight_s).
 long halo_big_min() {
-  static const long v = [] {
-    const char* e = getenv("RAFT_HALO_BIG_MIN");
-    return e ? atol(e) : 1L;
-  }();
+  static const long v = env_long("RAFT_HALO_BIG_MIN", 1L);
   return v;
 }
 double halo_big_cost() {
-  static const double v = [] {
-    const char* e = getenv("RAFT_HALO_BIG_COST");
-    return e ? atof(e) : 1.8;
-  }();
+  static const double v = env_double("RAFT_HALO_BIG_COST", 1.8);
   return v;
-}
-// the CU count of the device the launch runs on (the current device), cached per device: the tile
-// choice (rounds rule, tiles per work-group) follows it when one process drives several GPUs
-long halo_cus() {
-  constexpr int MAXDEV = 64;
-  static std::atomic<int> cache[MAXDEV];  // 0 = not queried yet
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return 256L;
-  if (dev >= 0 && dev < MAXDEV) {
-    const int c = cache[dev].load(std::memory_order_relaxed);
-    if (c > 0) return (long)c;
-  }
-  int cus = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-  if (dev >= 0 && dev < MAXDEV) cache[dev].store(cus, std::memory_order_relaxed);
-  return (long)cus;
 }
 bool halo_big_ok(const HaloOperands& o) {
   const raft_conv2d_params& p = o.p;
@@ -1316,7 +1329,7 @@ long halo_small_tiles(const HaloOperands& o) {  // 128-pixel x 64-column tiles
 }
 // the rounds rule above for a launch of big_tiles vs small_tiles work-groups
 bool halo_big_pays(long big_tiles, long small_tiles) {
-  const long mn = halo_big_min(), cus = halo_cus();
+  const long mn = halo_big_min(), cus = device_cus();
   if (mn <= 0 || big_tiles < mn) return false;
   return (double)cdiv_l(big_tiles, cus) * halo_big_cost() < (double)cdiv_l(small_tiles, cus);
 }
@@ -1327,10 +1340,7 @@ double halo_mt_plan_cost(const HaloOperands& o, int th);
 // multi-tile plans (a launch with rounds to spare runs several tiles per work-group, so whole rounds are
 // not the unit there): big tiles when cost(big) * RAFT_HALO_BIG_COST < cost(128-pixel)
 bool halo_big_mt() {
-  static const bool v = [] {
-    const char* e = getenv("RAFT_HALO_BIG_MT");
-    return e && e[0] == '1';
-  }();
+  static const bool v = env_on("RAFT_HALO_BIG_MT");
   return v;
 }
 // Tile rows of a conv's launch: HTH_BIG where the big tiles qualify and pay, and (the one-product
@@ -1352,35 +1362,16 @@ void halo_set_th(const HaloOperands& o, HaloArgs& a, int th) {
   }
 }
 
-// LDS left for the input-norm tables of a 3x3 ENC instantiation (halo_norm_bytes)
-template <int BNT, int WR, int TH>
-long halo_norm_cap_t() {
-  using C = HaloCfg<3, 3, BNT, WR, TH>;
-  return halo_norm_bytes<3, 3, BNT, RAFT_PREC_F16X3, true>(C::LDS_B, C::LDS_A, C::D);
-}
-long halo_norm_cap(int bn, int prec, int th) {
-  const bool x3 = prec == RAFT_PREC_F16X3;
-  if (th == HTH_BIG) return x3 ? halo_norm_cap_t<64, 128, HTH_BIG>() : halo_norm_cap_t<64, 64, HTH_BIG>();
-  if (bn == 64) return x3 ? halo_norm_cap_t<64, 128, HTH>() : halo_norm_cap_t<64, 64, HTH>();
-  return x3 ? halo_norm_cap_t<32, 128, HTH>() : halo_norm_cap_t<32, 64, HTH>();
-}
-
 // Tiles per work-group (halo_body): a launch with more tiles than CUs may run m spatial tiles per
 // work-group, the m of least cost in tile times (below), where padding every tile's K loop to
 // lcm(U, T) K-steps costs at most 1/8 and the input-norm tables of the images a work-group covers
 // fit its LDS; otherwise one tile per work-group.  RAFT_HALO_MT=0: always one.
 bool halo_mt_enabled() {
-  static const bool enabled = [] {
-    const char* e = getenv("RAFT_HALO_MT");
-    return !(e && e[0] == '0');
-  }();
-  return enabled;
+  static const bool off = env_off("RAFT_HALO_MT");
+  return !off;
 }
 double halo_mt_cost() {
-  static const double v = [] {
-    const char* e = getenv("RAFT_HALO_MT_COST");
-    return e ? atof(e) : 0.8;
-  }();
+  static const double v = env_double("RAFT_HALO_MT_COST", 0.8);
   return v;
 }
 bool halo_mt_ok(const HaloArgs& a, int bn, int th, long m) {
@@ -1403,7 +1394,7 @@ bool halo_mt_ok(const HaloArgs& a, int bn, int th, long m) {
 // sets l.m (spatial tiles per work-group) and l.grid0 for the launch of l.a[0] (and l.a[1] of a
 // pair, pair = true); returns the grid size (cost_out: the plan's cost in tile times)
 long halo_plan_grid(HaloLaunch& l, int bn, int th, bool pair, double* cost_out = nullptr) {
-  const long cus = halo_cus();
+  const long cus = device_cus();
   const long s0 = halo_spatial(l.a[0]), s1 = pair ? halo_spatial(l.a[1]) : 0;
   const long g0 = l.a[0].gn, g1 = pair ? l.a[1].gn : 0;
   auto wgs = [&](long m) { return g0 * cdiv_l(s0, m) + g1 * cdiv_l(s1, m); };
@@ -1429,11 +1420,17 @@ long halo_plan_grid(HaloLaunch& l, int bn, int th, bool pair, double* cost_out =
   return wgs(m);
 }
 
+// The N-tile width of a launch on th-row tiles that would have tiles64 tiles of 64 columns: one
+// work-group per CU (LDS), so 64 output channels per work-group unless 32 still fits the grid in one
+// round of 256 CUs with half of them idle at 64; the one-product modes' 128-column tiles (2 x 2 waves
+// of 64 x 64) where halo_pick says so
+int halo_bn(int th, bool wide, long tiles64) { return th == HTH_BIG ? 64 : wide ? 128 : tiles64 > 128 ? 64 : 32; }
+
 double halo_mt_plan_cost(const HaloOperands& o, int th) {
   HaloLaunch l;
   if (!halo_problem(o, l.a[0])) return 1e30;
   halo_set_th(o, l.a[0], th);
-  const int bn = th == HTH_BIG ? 64 : halo_spatial(l.a[0]) * (o.n_pad / 64) > 128 ? 64 : 32;
+  const int bn = halo_bn(th, false, halo_spatial(l.a[0]) * (o.n_pad / 64));
   l.a[0].gn = o.n_pad / bn;
   l.a[1] = l.a[0];
   double cost = 1e30;
@@ -1441,20 +1438,100 @@ double halo_mt_plan_cost(const HaloOperands& o, int th) {
   return cost;
 }
 
-// (q != nullptr: the form query, halo_start)
-void launch_halo(const HaloLaunch& l, int bn, int th, long wgs, hipStream_t s, ConvForm* q) {
-  const raft_conv2d_params& p = l.a[0].p;
-  dim3 grid((unsigned)wgs);
-  if (p.kh == 1 && p.kw == 1)
-    launch_halo_k<1, 1>(l, bn, th, grid, s, q);
-  else if (p.kh == 3)
-    launch_halo_k<3, 3>(l, bn, th, grid, s, q);
-  else if (p.kh == 1)
-    launch_halo_k<1, 5>(l, bn, th, grid, s, q);
-  else
-    launch_halo_k<5, 1>(l, bn, th, grid, s, q);
+// the least 128-column tile count for the wide tiles (RAFT_HALO_WIDE_MIN): 256, one round (512 until
+// r04j: config 5's bf16 update convs 364 -> 351 us per iteration, 47.0 -> 47.8 pairs/s on one box)
+long halo_wide_min() {
+  static const long v = env_long("RAFT_HALO_WIDE_MIN", 256L);
+  return v;
+}
+bool halo_wide_enabled() {
+  static const bool off = env_off("RAFT_HALO_WIDE");
+  return !off;
 }
 
+// The tile of a conv: the one-product modes' 128-column tiles (wide) where at least two rounds of
+// them remain (512), else the big tiles where the rounds rule picks them, else the wide tiles from
+// RAFT_HALO_WIDE_MIN (256) of them, else the 128-pixel tiles.  feat: the conv has an encoder feature
+// (stats_part / in_norm), which the wide tiles do not take.  Returns the tile rows; `wide` out.
+int halo_pick(const HaloOperands& o, const HaloArgs& a, bool feat, bool& wide) {
+  const bool can = o.p.precision != RAFT_PREC_F16X3 && !feat && o.n_pad % 128 == 0 && halo_wide_enabled();
+  const long n = halo_spatial(a) * (o.n_pad / 128);
+  wide = can && n >= 512;
+  const int th = halo_pick_th(o, wide);
+  if (!wide && th != HTH_BIG) wide = can && n >= halo_wide_min();
+  return th;
+}
+
+// Fills the plan of one conv (o1 == nullptr), or of two independent convs of one shape class and
+// precision in one launch (their tiles side by side in the grid, one N-tile width for both); false
+// where the halo kernel does not take the conv, or the two do not share a launch.
+// enc: plan the conv as with an encoder feature set.  The planner asks raft_conv2d_stats_slots and
+// raft_conv2d_in_norm_ok before it sets stats_part / in_norm, and sizes the partials buffer from the
+// answer, so both must be asked of the plan the conv will run with the feature on.
+bool halo_plan(const HaloOperands& o0, const HaloOperands* o1, bool enc, HaloPlan& pl) {
+  HaloLaunch& l = pl.l;
+  HaloForm& f = pl.f;
+  if (!halo_enabled() || !halo_problem(o0, l.a[0]) || (o1 && !halo_problem(*o1, l.a[1]))) return false;
+  const raft_conv2d_params& p = o0.p;
+  const bool feat = enc || p.stats_part || p.in_norm;
+  bool wide = false;
+  if (o1) {  // (raft_conv2d_pair takes no conv with a feature)
+    if (p.kh != o1->p.kh || p.kw != o1->p.kw || p.precision != o1->p.precision) return false;
+    // each conv's own tile rows (the rounds rule, as raft_conv2d would pick them): the big f16x3 tiles
+    // run the scaled one-chain arithmetic, so only convs that pick the same rows share a launch, which
+    // keeps the pair bit-identical to the two single launches (raft_hip.h); otherwise they run in order
+    f.th = halo_pick_th(o0, false);
+    if (halo_pick_th(*o1, false) != f.th) return false;
+  } else {
+    f.th = halo_pick(o0, l.a[0], feat, wide);
+  }
+  halo_set_th(o0, l.a[0], f.th);
+  if (o1) halo_set_th(*o1, l.a[1], f.th);
+  const long s0 = halo_spatial(l.a[0]), s1 = o1 ? halo_spatial(l.a[1]) : 0;
+  f.bn = halo_bn(f.th, wide, s0 * (o0.n_pad / 64) + (o1 ? s1 * (o1->n_pad / 64) : 0));
+  if (o0.n_pad % f.bn || (o1 && o1->n_pad % f.bn)) return false;
+  l.a[0].gn = o0.n_pad / f.bn;
+  if (o1)
+    l.a[1].gn = o1->n_pad / f.bn;
+  else
+    l.a[1] = l.a[0];
+  if (s0 * l.a[0].gn + (o1 ? s1 * l.a[1].gn : 0) >= (1L << 31)) return false;
+  f.wgs = halo_plan_grid(l, f.bn, f.th, o1 != nullptr);
+  f.m = l.m;
+  f.mt = l.m > 1;
+  // the instantiation: only the 1x1 and 3x3 convs have one with the encoder features, and it alone
+  // writes InstanceNorm partials, one slot per compute wave of a spatial tile
+  const bool k33 = p.kh == 3 && p.kw == 3;
+  f.enc = feat && (k33 || (p.kh == 1 && p.kw == 1));
+  f.stats_slots = f.enc ? l.a[0].tx_n * l.a[0].ty_n * 4 : 0;
+  // the input InstanceNorm in the loaders: the 3x3 convs' split-patch path (D = 3 for both N-tile
+  // widths), <= 256 input channels
+  f.norm_ok = k33 && p.in0_c <= 256 && HaloCfg<3, 3, 64>::D == 3 && HaloCfg<3, 3, 32>::D == 3;
+  // loader waves and compute waves per SIMD: the knobs choose among the forms that exist (the
+  // multi-tile body has the one form outside the encoders' 8 loaders)
+  const int prec = p.precision;
+  f.nl = 4;
+  f.ks = 1;
+  if (halo_can_nl8e(prec, f.enc, f.th, f.bn, p.kh, p.kw) && halo_nl8_enc()) {
+    f.nl = 8;
+  } else if (!f.mt) {
+    if (halo_can_ks2(prec, f.enc, f.th, f.bn, p.kh, p.kw) && halo_ks2())
+      f.ks = 2;
+    else if (halo_can_nl8(prec, f.enc, f.th, f.bn, p.kh, p.kw) && halo_nl8())
+      f.nl = 8;
+  }
+  return true;
+}
+
+void halo_form(const HaloForm& f, ConvForm* q) {
+  *q = ConvForm{};
+  q->kernel = RAFT_CONV_KERNEL_HALO;
+  q->tile_rows = f.th;
+  q->tile_cols = f.bn;
+  q->tiles_per_wg = f.m;
+  q->loader_waves = f.nl;
+  q->compute_waves_per_simd = f.ks;
+}
 
 }  // namespace
 
@@ -1486,137 +1563,38 @@ extern "C" int raft_conv2d_set_halo_ks(int ks) {
   return prev;
 }
 
-// whether the conv takes its input InstanceNorm in the loaders (raft_conv2d_params.in_norm): the
-// 3x3 convs' split-patch path (D = 3 for both N-tile widths), <= 256 input channels
-bool conv_halo_norm_ok(const HaloOperands& o) {
-  HaloArgs a;
-  if (!halo_enabled() || !halo_problem(o, a)) return false;
-  const raft_conv2d_params& p = o.p;
-  return p.kh == 3 && p.kw == 3 && p.in0_c <= 256 && HaloCfg<3, 3, 64>::D == 3 && HaloCfg<3, 3, 32>::D == 3;
-}
-
-// the least 128-column tile count for the wide tiles (RAFT_HALO_WIDE_MIN): 256, one round (512 until
-// r04j: config 5's bf16 update convs 364 -> 351 us per iteration, 47.0 -> 47.8 pairs/s on one box)
-long halo_wide_min() {
-  static const long v = [] {
-    const char* e = getenv("RAFT_HALO_WIDE_MIN");
-    return e ? atol(e) : 256L;
-  }();
-  return v;
-}
-bool halo_wide_enabled() {
-  static const bool enabled = [] {
-    const char* e = getenv("RAFT_HALO_WIDE");
-    return !(e && e[0] == '0');
-  }();
-  return enabled;
-}
-
-// The tile of a conv: the one-product modes' 128-column tiles (wide) where at least two rounds of
-// them remain (512), else the big tiles where the rounds rule picks them, else the wide tiles from
-// RAFT_HALO_WIDE_MIN (256) of them, else the 128-pixel tiles.  Returns the tile rows; `wide` out.
-int halo_pick(const HaloOperands& o, const HaloArgs& a, bool& wide) {
-  const raft_conv2d_params& p = o.p;
-  const bool can = p.precision != RAFT_PREC_F16X3 && !p.stats_part && !p.in_norm && o.n_pad % 128 == 0 &&
-                   halo_wide_enabled();
-  const long n = halo_spatial(a) * (o.n_pad / 128);
-  wide = can && n >= 512;
-  const int th = halo_pick_th(o, wide);
-  if (!wide && th != HTH_BIG) wide = can && n >= halo_wide_min();
-  return th;
-}
-
-// tile rows conv_halo_launch picks for the conv (HTH or HTH_BIG), 0 when the halo kernel does not run it
-int conv_halo_tile_rows(const HaloOperands& o) {
-  HaloArgs a;
-  if (!halo_enabled() || !halo_problem(o, a)) return 0;
-  bool wide;
-  return halo_pick(o, a, wide);
-}
-
-bool conv_halo_covers(const HaloOperands& o) {
-  HaloArgs a;
-  return halo_enabled() && halo_problem(o, a);
-}
-
-int conv_halo_stats_slots(const HaloOperands& o) {
-  HaloArgs a;
-  if (!halo_enabled() || !halo_problem(o, a)) return 0;
-  // only the ENC instantiations (1x1 and 3x3, launch_halo_p) write InstanceNorm partials: one slot
-  // per compute wave of a spatial tile (the tile rows of conv_halo_launch's pick)
-  if (!((o.p.kh == 1 && o.p.kw == 1) || (o.p.kh == 3 && o.p.kw == 3))) return 0;
-  const int th = halo_pick_th(o, false);  // (ENC convs never take the 128-column tiles)
-  return a.tx_n * cdiv(o.p.out_h, th) * 4;
-}
-
-// the launch of one conv: operands, N-tile width, tile rows and grid size; false when the halo
-// kernel does not cover the conv
-static bool halo_plan(const HaloOperands& o, HaloLaunch& l, int& bn, int& th, long& wgs) {
-  if (!halo_enabled() || !halo_problem(o, l.a[0])) return false;
-  const long spatial = halo_spatial(l.a[0]);
-  // one work-group per CU (LDS): 64 output channels per work-group unless
-  // 32 still fits the grid in one round of 256 CUs with half of them idle at 64;
-  // the one-product modes take 128-column tiles (2 x 2 waves of 64 x 64) by halo_pick
-  // (RAFT_HALO_WIDE=0: never)
-  bool wide;
-  th = halo_pick(o, l.a[0], wide);
-  bn = th == HTH_BIG ? 64 : wide ? 128 : spatial * (o.n_pad / 64) > 128 ? 64 : 32;
-  halo_set_th(o, l.a[0], th);
-  l.a[0].gn = o.n_pad / bn;
-  const long tiles = halo_spatial(l.a[0]) * l.a[0].gn;
-  if (tiles >= (1L << 31)) return false;
-  l.a[1] = l.a[0];
-  wgs = halo_plan_grid(l, bn, th, false);
+bool conv_halo_plan(const HaloOperands& o, bool enc, HaloForm& f) {
+  HaloPlan pl;
+  if (!halo_plan(o, nullptr, enc, pl)) return false;
+  f = pl.f;
   return true;
-}
-
-// tiles per work-group of the conv's halo launch (halo_body), 0 when the halo kernel does not run it
-int conv_halo_tiles_per_wg(const HaloOperands& o) {
-  HaloLaunch l;
-  int bn, th;
-  long wgs;
-  return halo_plan(o, l, bn, th, wgs) ? l.m : 0;
 }
 
 // Launches the halo kernel when the conv is one it covers; returns 1 without launching
 // otherwise.  Arguments are already validated by raft_conv2d.
-// q != nullptr (raft_conv2d_form): the same plan and dispatch, but *q is filled instead of the launch.
+// q != nullptr (raft_conv2d_form): the plan's form is written to *q and nothing is launched.
 int conv_halo_launch(const HaloOperands& o, hipStream_t s, ConvForm* q) {
-  HaloLaunch l;
-  int bn, th;
-  long wgs;
-  if (!halo_plan(o, l, bn, th, wgs)) return 1;
-  launch_halo(l, bn, th, wgs, s, q);
+  HaloPlan pl;
+  if (!halo_plan(o, nullptr, false, pl)) return 1;
+  if (q)
+    halo_form(pl.f, q);
+  else
+    launch_halo(pl, s);
   return 0;
 }
 
-// Two independent convs of one shape class and precision in one launch (their tiles side
-// by side in the grid, one N-tile width for both); returns 1 without launching when the
-// pair does not qualify.
+// The pair: returns 1 without launching when the two do not share a launch.
 // q != nullptr (raft_conv2d_pair_form): q[0] = q[1] = the shared launch's form, nothing launched.
 int conv_halo_launch_pair(const HaloOperands& o0, const HaloOperands& o1, hipStream_t s, ConvForm* q) {
-  HaloLaunch l;
-  if (!halo_enabled() || !halo_problem(o0, l.a[0]) || !halo_problem(o1, l.a[1])) return 1;
-  const raft_conv2d_params &p0 = o0.p, &p1 = o1.p;
-  if (p0.kh != p1.kh || p0.kw != p1.kw || p0.precision != p1.precision) return 1;
-  // each conv's own tile rows (the rounds rule, as raft_conv2d would pick them): the big f16x3 tiles
-  // run the scaled one-chain arithmetic, so only convs that pick the same rows share a launch, which
-  // keeps the pair bit-identical to the two single launches (raft_hip.h); otherwise they run in order
-  const int th = halo_pick_th(o0, false);
-  if (halo_pick_th(o1, false) != th) return 1;
-  halo_set_th(o0, l.a[0], th);
-  halo_set_th(o1, l.a[1], th);
-  const long s0 = halo_spatial(l.a[0]), s1 = halo_spatial(l.a[1]);
-  const int bn = th == HTH_BIG ? 64 : s0 * (o0.n_pad / 64) + s1 * (o1.n_pad / 64) > 128 ? 64 : 32;
-  if (o0.n_pad % bn || o1.n_pad % bn) return 1;
-  l.a[0].gn = o0.n_pad / bn;
-  l.a[1].gn = o1.n_pad / bn;
-  const long t0 = s0 * l.a[0].gn, tiles = t0 + s1 * l.a[1].gn;
-  if (tiles >= (1L << 31)) return 1;
-  launch_halo(l, bn, th, halo_plan_grid(l, bn, th, true), s, q);
-  if (q) q[1] = q[0];
+  HaloPlan pl;
+  if (!halo_plan(o0, &o1, false, pl)) return 1;
+  if (q) {
+    halo_form(pl.f, &q[0]);
+    q[1] = q[0];
+  } else {
+    launch_halo(pl, s);
+  }
   return 0;
 }
-
 
 }  // namespace raft

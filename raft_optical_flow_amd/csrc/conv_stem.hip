@@ -172,11 +172,8 @@ __global__ __launch_bounds__(256, 3) void conv_stem_kernel(StemArgs sa) {  // 3 
 
 namespace {
 bool stem_covers(const raft_conv2d_params& p, int k_pad) {
-  static const bool enabled = [] {
-    const char* e = getenv("RAFT_CONV_STEM");
-    return !(e && e[0] == '0');
-  }();
-  if (!enabled) return false;
+  static const bool off = env_off("RAFT_CONV_STEM");
+  if (off) return false;
   if (p.mode != RAFT_CONV_GATHER || p.kh != ST_K || p.kw != ST_K || p.stride_h != ST_S || p.stride_w != ST_S ||
       p.in0_c != ST_C || p.in1_c != 0 || p.n != ST_N || k_pad != ST_KS * 32)
     return false;

@@ -1208,13 +1208,6 @@ __global__ void corr_lookup_generic_kernel(LookupArgs a) {
   }
 }
 
-int grid_for(long n, int block = 256) {
-  long g = (n + block - 1) / block;
-  if (g > 65536) g = 65536;
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
 // level geometry; returns false if a level is empty
 bool pyramid_levels(int B, int H, int W, int L, Level* lv) {
   long off = 0;
@@ -1233,6 +1226,25 @@ bool pyramid_levels(int B, int H, int W, int L, Level* lv) {
     w /= 2;
   }
   return true;
+}
+
+// non-temporal pyramid stores when level 0 alone is far past the 256 MiB Infinity Cache (the lookups
+// then read it from HBM either way); RAFT_CORR_NT=0 / 1 overrides (read on every call)
+bool corr_nt(int B, long P, const Level& l0) {
+  if (env_on("RAFT_CORR_NT")) return true;
+  return !env_off("RAFT_CORR_NT") && 4.0 * B * (double)P * l0.mapsz > 512.0 * 1024 * 1024;
+}
+
+// levels from .. L-1 of the pyramid, each pooled from the one above it
+int pool_levels(float* pyramid, int B, long P, const Level* lv, int from, int L, hipStream_t s, const char* what) {
+  for (int l = from; l < L; ++l) {
+    const long n = (long)B * P * lv[l].mapsz;
+    hipLaunchKernelGGL(pool2_tiled_kernel, dim3(grid_for(n)), dim3(256), 0, s, pyramid, pyramid, (long)B * P, lv[l - 1],
+                       lv[l]);
+    const int rc = check_launch(what);
+    if (rc) return rc;
+  }
+  return 0;
 }
 
 }  // namespace
@@ -1286,18 +1298,9 @@ extern "C" int raft_corr_build_prec(const float* fmap1, const float* fmap2, int 
   a.has_l1 = L > 1;
   a.l1 = lv[L > 1 ? 1 : 0];
   a.nbx = cdiv(W, 8);
-  {
-    // non-temporal pyramid stores when level 0 alone is far past the 256 MiB Infinity Cache (the
-    // lookups then read it from HBM either way); RAFT_CORR_NT=0 / 1 overrides
-    const char* e = getenv("RAFT_CORR_NT");
-    const double l0_bytes = 4.0 * B * (double)P * lv[0].mapsz;
-    a.nt = e && (e[0] == '0' || e[0] == '1') ? e[0] == '1' : l0_bytes > 512.0 * 1024 * 1024;
-  }
+  a.nt = corr_nt(B, P, lv[0]);
   hipStream_t s = as_stream(stream);
-  static const bool big = [] {
-    const char* e = getenv("RAFT_CORR_BUILD_BIG");
-    return !(e && e[0] == '0');
-  }();
+  static const bool big = !env_off("RAFT_CORR_BUILD_BIG");
   if (precision == RAFT_PREC_FP32) {
     dim3 grid(cdiv((int)P, CB_BM), cdiv(H, 8) * a.nbx, B);
     hipLaunchKernelGGL(corr_build_kernel<false>, grid, dim3(256), 0, s, a);
@@ -1322,16 +1325,8 @@ extern "C" int raft_corr_build_prec(const float* fmap1, const float* fmap2, int 
     dim3 grid(cdiv((int)P, CB_BM), cdiv(H, 8) * a.nbx, B);
     hipLaunchKernelGGL(corr_build_kernel<true>, grid, dim3(256), 0, s, a);
   }
-  int rc = check_launch("raft_corr_build");
-  if (rc) return rc;
-  for (int l = 2; l < L; ++l) {
-    const long n = (long)B * P * lv[l].mapsz;
-    hipLaunchKernelGGL(pool2_tiled_kernel, dim3(grid_for(n)), dim3(256), 0, s, pyramid, pyramid, (long)B * P, lv[l - 1],
-                       lv[l]);
-    rc = check_launch("raft_corr_build(pool)");
-    if (rc) return rc;
-  }
-  return 0;
+  const int rc = check_launch("raft_corr_build");
+  return rc ? rc : pool_levels(pyramid, B, P, lv, 2, L, s, "raft_corr_build(pool)");
 }
 
 #ifdef CB4_STAMPS
@@ -1350,8 +1345,7 @@ namespace raft {
 // 16 with >= 4 half-steps, 32-bit map offsets, RAFT_CORR_BUILD4 not 0 (the operand checks -- ld, alignment,
 // a workspace -- come on top, per call)
 static bool corr_build4_shape(int B, int H, int W, int C, int precision) {
-  const char* e = getenv("RAFT_CORR_BUILD4");
-  if (e && e[0] == '0') return false;
+  if (env_off("RAFT_CORR_BUILD4")) return false;  // (read on every call)
   return precision == RAFT_PREC_F16X3 && C % 16 == 0 && C >= 64 && C <= 1024 && B > 0 && H > 0 && W > 0 &&
          (double)B * H * W * C * 4 < 2147483648.0;
 }
@@ -1403,35 +1397,21 @@ extern "C" int raft_corr_build_ws(const float* fmap1, const float* fmap2, int ld
   a.l1 = lv[L > 1 ? 1 : 0];
   a.l2 = lv[L > 2 ? 2 : 0];
   // level 2 from the build's registers (RAFT_CB4_L2=0: from level 1 by pool2_tiled_kernel, the same bytes)
-  static const bool l2_on = [] {
-    const char* e = getenv("RAFT_CB4_L2");
-    return !(e && e[0] == '0');
-  }();
-  const bool l2 = l2_on && L > 2;
-  {
-    const char* e = getenv("RAFT_CORR_NT");
-    const double l0_bytes = 4.0 * B * (double)P * lv[0].mapsz;
-    a.nt = e && (e[0] == '0' || e[0] == '1') ? e[0] == '1' : l0_bytes > 512.0 * 1024 * 1024;
-  }
+  static const bool l2_off = env_off("RAFT_CB4_L2");
+  const bool l2 = !l2_off && L > 2;
+  a.nt = corr_nt(B, P, lv[0]);
   // RAFT_CB4_W4=1: 4-wave work-groups, two per CU (r05p: config 2's map 156 -> 142 us alone, config 4's
   // 1.50 -> 1.54 ms, config 5's 2.47 -> 2.80 ms: the half-size units move 1.5x the operand bytes per
   // flop; the forward unchanged at config 2, 1.5 % slower at config 5), default: 8 waves, one per CU
   // (read per call, like RAFT_CB_ORDER: a test can switch it; a plan captures the launch it made)
-  const bool w4 = [] {
-    const char* e = getenv("RAFT_CB4_W4");
-    return e && e[0] == '1';
-  }();
+  const bool w4 = env_on("RAFT_CB4_W4");
   a.qt = (int)cdiv_l(P, w4 ? CB4_T / 2 : CB4_T);
   a.ttx = cdiv(W, 16);
   a.tt = cdiv(H, 16) * a.ttx;
   a.units = (long)B * a.qt * a.tt;
   a.sink = reinterpret_cast<f32x4*>(s2 + map_bytes);
-  int cus = 256, dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-      cus <= 0)
-    cus = 256;
   // persistent: one 8-wave work-group per CU (128 KiB LDS) or two 4-wave ones (72 KiB each)
-  const long wgs = w4 ? 2L * cus : (long)cus;
+  const long wgs = (w4 ? 2L : 1L) * device_cus();
   const dim3 grid((unsigned)(a.units < wgs ? a.units : wgs));
   if (w4) {
     if (l2)
@@ -1448,15 +1428,7 @@ extern "C" int raft_corr_build_ws(const float* fmap1, const float* fmap2, int ld
     hipLaunchKernelGGL(corr_build4_kernel<false>, grid, dim3(512), 0, s, a);
   }
   rc = check_launch("raft_corr_build_ws");
-  if (rc) return rc;
-  for (int l = l2 ? 3 : 2; l < L; ++l) {
-    const long n = (long)B * P * lv[l].mapsz;
-    hipLaunchKernelGGL(pool2_tiled_kernel, dim3(grid_for(n)), dim3(256), 0, s, pyramid, pyramid, (long)B * P, lv[l - 1],
-                       lv[l]);
-    rc = check_launch("raft_corr_build_ws(pool)");
-    if (rc) return rc;
-  }
-  return 0;
+  return rc ? rc : pool_levels(pyramid, B, P, lv, l2 ? 3 : 2, L, s, "raft_corr_build_ws(pool)");
 }
 
 extern "C" int raft_corr_pyramid_level(const float* pyramid, int B, int H, int W, int L, int level, float* out,

@@ -186,11 +186,6 @@ __global__ __launch_bounds__(256) void stream_carry_n_kernel(CarryNArgs a) {
   }
 }
 
-int grid_for(long n) {
-  long g = (n + 255) / 256;
-  return (int)(g > 65536 ? 65536 : g < 1 ? 1 : g);
-}
-
 }  // namespace
 }  // namespace raft
 

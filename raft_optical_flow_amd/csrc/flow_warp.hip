@@ -287,11 +287,6 @@ __global__ __launch_bounds__(256) void splat_convert_kernel(SplatArgs a) {
     a.density[i] = (float)a.ws[i] * 2.3283064365386963e-10f;   // one rounding (the cast); * 2^-32 is exact
 }
 
-int grid_for(long n) {
-  long g = (n + 255) / 256;
-  return (int)(g > 65536 ? 65536 : g < 1 ? 1 : g);
-}
-
 bool warp_size_ok(int B, int H, int W) { return B > 0 && H > 0 && W > 0 && (long)B * H * W < (1L << 30); }
 
 }  // namespace

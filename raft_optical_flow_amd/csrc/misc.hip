@@ -11,13 +11,6 @@ char* last_error_buf() {
 
 namespace {
 
-int grid_for(long n, int block = 256) {
-  long g = (n + block - 1) / block;
-  if (g > 65536) g = 65536;
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
 #define GRID_STRIDE(i, total) \
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < (total); i += (long)gridDim.x * blockDim.x)
 
