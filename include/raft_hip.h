@@ -801,6 +801,83 @@ size_t raft_splat_ws_bytes(int B, int H, int W);
 int raft_splat_density(const float* flow, long batch_stride, long chan_stride, long pitch, int top, int left, int B,
                        int H, int W, void* ws, float* density, raft_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * Scoring a flow against ground truth (utils.flow_errors, utils.FlowMetrics): what evaluate.py's
+ * validate_chairs / validate_sintel / validate_kitti compute on the host, on the device.
+ * Additive entries: RAFT_HIP_ABI_VERSION stays 19.
+ * --------------------------------------------------------------------------- */
+/* Definition.  At a valid pixel with prediction (u, v) = flow and ground truth (gu, gv) = flow_gt, in IEEE
+ * fp32 with every operation rounded to nearest and nothing fused:
+ *   du = u - gu, dv = v - gv
+ *   epe   = sqrt(du * du + dv * dv)          the end-point error: torch.sum((flow - flow_gt)**2, dim=0).sqrt()
+ *   mag   = sqrt(gu * gu + gv * gv)
+ *   ratio = epe / mag                         (mag == 0 gives inf or NaN; the comparisons below decide)
+ * A pixel is valid when both hold:
+ *   mask      valid == NULL, or the mask says so: RAFT_MASK_U8 (bool or uint8, one byte) != 0;
+ *             RAFT_MASK_F32 >= 0.5f (validate_kitti's `valid_gt >= 0.5`); a NaN mask value fails.
+ *   gt_limit  gt_limit <= 0 (absent), or |gu| < gt_limit and |gv| < gt_limit (core/datasets.py's
+ *             `(flow.abs() < 1000)`); a NaN fails.
+ * An invalid pixel counts nowhere.  A valid pixel whose epe is not finite counts in RAFT_FM_N and
+ * RAFT_FM_N_NONFINITE only.  Every other valid pixel counts in
+ *   RAFT_FM_N_LT1 / _LT3 / _LT5    epe < 1, epe < 3, epe < 5 (strict, as the reference's np.mean(epe < k))
+ *   RAFT_FM_N_OUTLIER              epe > 3 && ratio > 0.05 (KITTI's Fl, the reference's comparisons verbatim)
+ *   RAFT_FM_N_S0_10 / _S10_40 / _S40   Sintel's speed classes on mag: mag < 10; 10 <= mag < 40; mag >= 40
+ *   RAFT_FM_EPE_SUM                the fp64 sum of the fp32 epe values, and per speed class
+ *   RAFT_FM_EPE_SUM_S0_10 / _S10_40 / _S40.
+ *
+ * Record.  RAFT_FLOW_METRICS_SLOTS = 16 slots of 64 bits per sample: counts are int64, sums are fp64
+ * stored by their bits.  `record` is [B][16]; `totals`, if given, is one record that the call ADDS every
+ * sample's record into (zero it before the first call; calls accumulate in stream order), together with
+ *   RAFT_FM_IMAGES           the number of samples with n > 0
+ *   RAFT_FM_IMAGE_MEAN_SUM   the fp64 sum of epe_sum / n over those samples (validate_kitti reports the mean
+ *                            of per-image means)
+ * which are 0 in a sample's record, as is RAFT_FM_RESERVED (written as 0).
+ *
+ * Reproducibility.  Two launches: every work-group sums its pixels (threads in fp64 and integers, the
+ * wave by a butterfly, the waves through LDS in order) and writes one partial record to ws; one work-group
+ * adds the partials in index order, writes the records and adds them to the totals in sample order, in
+ * one thread.  No atomics.  The grid depends on (H, W) only: min(ceil(H * W / RAFT_FLOW_METRICS_BLOCK_PIXELS),
+ * RAFT_FLOW_METRICS_MAX_BLOCKS) work-groups per sample, never spanning two samples.  Two runs are bitwise
+ * equal on any device, and a sample's record does not depend on its batch index or on the other samples.
+ * Any other order of the same fp64 sum lies within n * 2^-53 * sum |epe| of it.
+ *
+ * Layout.  flow and flow_gt: float32 NCHW with unit element stride, element (b, c, y, x) at
+ * p[b * batch_stride + c * chan_stride + y * pitch + x] (strides in floats, pitch >= W): a crop of a
+ * padded flow_up (InputPadder.unpad's view) is read in place by passing the crop's first element.  valid:
+ * [B][H][W] with a batch stride and a row pitch in elements, or NULL (then its tag and strides are not
+ * read).  epe_map, if given: float32 [B][H][W] dense, the fp32 epe per pixel, NaN at invalid pixels (every
+ * NaN written is the quiet NaN 0x7fc00000).  ws: raft_flow_metrics_ws_bytes(B, H, W) bytes, needs no
+ * initialisation.  flow, flow_gt, a float32 mask and epe_map are 4-byte aligned, record, totals and ws
+ * 8-byte.  No output aliases an input or another output.  B * H * W < 2^30. */
+#define RAFT_FLOW_METRICS_SLOTS 16
+#define RAFT_FLOW_METRICS_BLOCK_PIXELS 1024 /* pixels a work-group takes per pass */
+#define RAFT_FLOW_METRICS_MAX_BLOCKS 256    /* work-groups per sample at most; larger samples wrap */
+#define RAFT_FM_N 0
+#define RAFT_FM_N_NONFINITE 1
+#define RAFT_FM_N_LT1 2
+#define RAFT_FM_N_LT3 3
+#define RAFT_FM_N_LT5 4
+#define RAFT_FM_N_OUTLIER 5
+#define RAFT_FM_N_S0_10 6
+#define RAFT_FM_N_S10_40 7
+#define RAFT_FM_N_S40 8
+#define RAFT_FM_EPE_SUM 9
+#define RAFT_FM_EPE_SUM_S0_10 10
+#define RAFT_FM_EPE_SUM_S10_40 11
+#define RAFT_FM_EPE_SUM_S40 12
+#define RAFT_FM_IMAGES 13
+#define RAFT_FM_IMAGE_MEAN_SUM 14
+#define RAFT_FM_RESERVED 15
+#define RAFT_MASK_U8 0  /* bool or uint8: valid where != 0 */
+#define RAFT_MASK_F32 1 /* float32: valid where >= 0.5 */
+/* bytes of raft_flow_metrics' workspace; 0 for sizes it rejects */
+size_t raft_flow_metrics_ws_bytes(int B, int H, int W);
+int raft_flow_metrics(const float* flow, long flow_batch_stride, long flow_chan_stride, long flow_pitch,
+                      const float* flow_gt, long gt_batch_stride, long gt_chan_stride, long gt_pitch,
+                      const void* valid, int valid_dtype, long valid_batch_stride, long valid_pitch, int B, int H,
+                      int W, float gt_limit, void* record, void* totals, float* epe_map, void* ws,
+                      raft_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

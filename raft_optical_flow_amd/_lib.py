@@ -42,6 +42,19 @@ VIZ_CLIP = 4   # clip both components to [0, clip_flow] first
 
 WARP_BORDER = 1   # raft_warp_frame flag: clamp the sampling position to the frame (default: zeros outside)
 
+MASK_U8 = 0    # raft_flow_metrics mask tags: bool or uint8, valid where != 0
+MASK_F32 = 1   # float32, valid where >= 0.5
+
+# raft_flow_metrics: the record's slots (RAFT_FM_*), int64 counts then fp64 sums, and the launch constants
+FM_SLOTS = 16
+FM_BLOCK_PIXELS = 1024
+FM_MAX_BLOCKS = 256
+FM_COUNTS = ("n", "n_nonfinite", "n_lt1", "n_lt3", "n_lt5", "n_outlier", "n_s0_10", "n_s10_40", "n_s40")
+FM_SUMS = ("epe_sum", "epe_sum_s0_10", "epe_sum_s10_40", "epe_sum_s40")
+FM_IMAGES = 13
+FM_IMAGE_MEAN_SUM = 14
+FM_RESERVED = 15
+
 EPI_LINEAR = 0
 EPI_RELU = 1
 EPI_RESID_RELU = 2
@@ -210,6 +223,9 @@ _PROTOS = {
                                 c_int, c_int, c_int, c_int, P, c_int, P, P]),
     "raft_splat_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "raft_splat_density": (c_int, [P, c_long, c_long, c_long, c_int, c_int, c_int, c_int, c_int, P, P, P]),
+    "raft_flow_metrics_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "raft_flow_metrics": (c_int, [P, c_long, c_long, c_long, P, c_long, c_long, c_long, P, c_int, c_long, c_long,
+                                  c_int, c_int, c_int, c_float, P, P, P, P, P]),
 }
 
 EXPORTED = tuple(_PROTOS)

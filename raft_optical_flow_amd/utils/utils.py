@@ -21,12 +21,21 @@
   splat_density        unflow_ops_pytorch.py:6-85   UnFlow's forward-warp density, every contribution summed
                                                    (the reference's indexed `+=` keeps the last write only),
                                                    bitwise reproducible (raft_splat_density)
+  flow_errors          evaluate.py:87, :115,       per-sample error statistics of a flow against ground truth, on
+                       :148-157                    the device (raft_flow_metrics): the EPE sum, the 1 / 3 / 5 px
+                                                   counts, KITTI's outliers, Sintel's speed classes
+  FlowMetrics          evaluate.py:75-166          those statistics accumulated over a dataset without a copy or
+                                                   a synchronisation per pair: validate_chairs reads "epe",
+                                                   validate_sintel "epe", "1px", "3px", "5px", validate_kitti
+                                                   "epe_image_mean" and "f1"
 
 Every helper computes on the GPU through the HIP kernels of libraft_hip.so; a CPU tensor is
 copied to the current GPU and the result copied back (there is no host computation path).
 Kernels run on the tensor's own device (its current stream), whatever device is current.
 """
 from __future__ import annotations
+
+import collections
 
 import torch
 
@@ -344,3 +353,162 @@ def splat_density(flow):
         out = torch.empty(b, 1, h, w, device=fl.device)
         L.call("raft_splat_density", fl.data_ptr(), *sfl, 0, 0, b, h, w, ws.data_ptr(), out.data_ptr(), _stream())
     return out
+
+
+FlowErrors = collections.namedtuple(
+    "FlowErrors", ("n", "n_nonfinite", "n_lt1", "n_lt3", "n_lt5", "n_outlier", "n_s0_10", "n_s10_40", "n_s40",
+                   "epe_sum", "epe_sum_s0_10", "epe_sum_s10_40", "epe_sum_s40", "epe_map"))
+FlowErrors.__doc__ = """Per-sample error statistics of flow_errors: device tensors [B], the counts int64 and the sums
+float64 (include/raft_hip.h names the slots); epe_map float32 [B,1,H,W] or None."""
+
+
+def _check_metrics_args(name, flow, flow_gt, valid, gt_limit):
+    """The type, shape and value checks of flow_errors / FlowMetrics.update (no device work): returns
+    (b, h, w, gt_limit as a float, 0.0 for none)."""
+    b, h, w = _check_flow(name, flow)
+    if not torch.is_tensor(flow_gt):
+        raise TypeError(f"{name}: flow_gt must be a tensor, got {type(flow_gt).__name__}")
+    if flow_gt.dtype != torch.float32:
+        raise TypeError(f"{name}: flow_gt must be float32, got {flow_gt.dtype}")
+    if tuple(flow_gt.shape) != tuple(flow.shape):
+        raise ValueError(f"{name}: flow_gt {tuple(flow_gt.shape)} and flow {tuple(flow.shape)} differ in shape")
+    if valid is not None:
+        if not torch.is_tensor(valid):
+            raise TypeError(f"{name}: valid must be a tensor or None, got {type(valid).__name__}")
+        if valid.dtype not in (torch.bool, torch.uint8, torch.float32):
+            raise TypeError(f"{name}: valid must be bool, uint8 or float32, got {valid.dtype}")
+        if tuple(valid.shape) not in ((b, h, w), (b, 1, h, w)):
+            raise ValueError(f"{name}: valid must be [B, H, W] or [B, 1, H, W] = {(b, h, w)}, got "
+                             f"{tuple(valid.shape)}")
+    return b, h, w, _check_gt_limit(name, gt_limit)
+
+
+def _check_gt_limit(name, gt_limit):
+    if gt_limit is None:
+        return 0.0
+    if isinstance(gt_limit, bool) or not isinstance(gt_limit, (int, float)):
+        raise TypeError(f"{name}: gt_limit must be a number or None, got {type(gt_limit).__name__}")
+    if not (0.0 < float(gt_limit) < float("inf")):
+        raise ValueError(f"{name}: gt_limit must be positive and finite (None: no limit), got {gt_limit!r}")
+    return float(gt_limit)
+
+
+def _check_metrics_devices(name, flow, flow_gt, valid):
+    for what, t in (("flow", flow), ("flow_gt", flow_gt), ("valid", valid)):
+        if t is not None and not t.is_cuda:
+            raise RuntimeError(f"{name} runs on a ROCm GPU only: {what} is on {t.device} (no CPU path)")
+    for what, t in (("flow_gt", flow_gt), ("valid", valid)):
+        if t is not None and t.device != flow.device:
+            raise RuntimeError(f"{name}: {what} is on {t.device}, flow on {flow.device}")
+
+
+def _flow_metrics_call(flow, flow_gt, valid, limit, b, h, w, totals, want_map):
+    """One raft_flow_metrics call on flow's device (current): (record int64 [B,16], epe_map or None)."""
+    L = _lib()
+    dev = flow.device
+    fl, sfl = _pitched(flow, h, w)
+    gt, sgt = _pitched(flow_gt, h, w)
+    vp, tag, svb, svp = None, 0, 0, 0
+    if valid is not None:
+        v = valid.reshape(b, h, w) if valid.dim() == 4 else valid
+        if v.stride(2) != 1 and w > 1 or (h > 1 and v.stride(1) < w):
+            v = v.contiguous()
+        tag = L.MASK_F32 if v.dtype == torch.float32 else L.MASK_U8
+        vp, svb, svp = v.data_ptr(), v.stride(0), (v.stride(1) if h > 1 else w)
+    record = torch.empty(b, L.FM_SLOTS, dtype=torch.int64, device=dev)
+    ws = torch.empty(L.load().raft_flow_metrics_ws_bytes(b, h, w) // 8, dtype=torch.int64, device=dev)
+    emap = torch.empty(b, 1, h, w, dtype=torch.float32, device=dev) if want_map else None
+    L.call("raft_flow_metrics", fl.data_ptr(), *sfl, gt.data_ptr(), *sgt, vp, tag, svb, svp, b, h, w, limit,
+           record.data_ptr(), None if totals is None else totals.data_ptr(),
+           None if emap is None else emap.data_ptr(), ws.data_ptr(), _stream())
+    return record, emap
+
+
+def flow_errors(flow, flow_gt, valid=None, gt_limit=None, epe_map=False):
+    """Error statistics of a flow against ground truth per sample (raft_flow_metrics: one call, two launches, no
+    synchronisation): what evaluate.py's validate_* functions compute on the host from `.cpu()` copies.
+
+    flow, flow_gt: float32 [B,2,H,W] GPU tensors of any strides (InputPadder.unpad's view of a padded flow_up is
+    read in place).  valid: None, or bool / uint8 (valid where nonzero) / float32 (valid where >= 0.5, as
+    validate_kitti's `valid_gt >= 0.5`), [B,H,W] or [B,1,H,W].  gt_limit: None, or ground truth with |gu| or |gv|
+    >= gt_limit is invalid (core/datasets.py uses 1000).  Per valid pixel, in IEEE fp32: epe = sqrt(du^2 + dv^2),
+    mag = sqrt(gu^2 + gv^2).  Returns a FlowErrors namedtuple of device tensors [B]: int64 counts n, n_nonfinite
+    (valid pixels whose epe is not finite: counted in n and there only), n_lt1 / n_lt3 / n_lt5 (epe < 1, 3, 5),
+    n_outlier (epe > 3 and epe / mag > 0.05: KITTI's Fl), n_s0_10 / n_s10_40 / n_s40 (Sintel's speed classes on
+    mag), float64 sums epe_sum and epe_sum_s0_10 / _s10_40 / _s40, and epe_map (float32 [B,1,H,W], NaN at invalid
+    pixels) if asked for, else None.  Bitwise reproducible; include/raft_hip.h has the definition."""
+    b, h, w, limit = _check_metrics_args("flow_errors", flow, flow_gt, valid, gt_limit)
+    _check_metrics_devices("flow_errors", flow, flow_gt, valid)
+    L = _lib()
+    with torch.cuda.device(flow.device):
+        record, emap = _flow_metrics_call(flow, flow_gt, valid, limit, b, h, w, None, bool(epe_map))
+    sums = record.view(torch.float64)
+    nc = len(L.FM_COUNTS)
+    return FlowErrors(*[record[:, i] for i in range(nc)], *[sums[:, nc + i] for i in range(len(L.FM_SUMS))], emap)
+
+
+class FlowMetrics:
+    """Running error statistics over a dataset, kept on the device: evaluate.py's validate_* loops without the
+    per-pair `.cpu()` copy and synchronisation.
+
+        m = FlowMetrics()                        # validate_sintel / validate_chairs
+        for ...: m.update(padder.unpad(flow_up), flow_gt)
+        r = m.result()                           # r["epe"], r["1px"], r["3px"], r["5px"]
+
+        m = FlowMetrics()                        # validate_kitti
+        for ...: m.update(padder.unpad(flow_up), flow_gt, valid_gt)
+        r = m.result()                           # r["epe_image_mean"], r["f1"]
+
+    update() takes what flow_errors takes (shapes may change from call to call) and adds into device totals
+    without synchronising; result() synchronises once.  gt_limit as in flow_errors."""
+
+    def __init__(self, gt_limit=None):
+        self.gt_limit = _check_gt_limit("FlowMetrics", gt_limit)
+        self._totals = None
+
+    def update(self, flow, flow_gt, valid=None):
+        b, h, w, _ = _check_metrics_args("FlowMetrics.update", flow, flow_gt, valid, None)
+        _check_metrics_devices("FlowMetrics.update", flow, flow_gt, valid)
+        if self._totals is not None and self._totals.device != flow.device:
+            raise RuntimeError(f"FlowMetrics.update: the totals are on {self._totals.device}, flow on {flow.device}")
+        with torch.cuda.device(flow.device):
+            if self._totals is None:
+                self._totals = torch.zeros(_lib().FM_SLOTS, dtype=torch.int64, device=flow.device)
+            _flow_metrics_call(flow, flow_gt, valid, self.gt_limit, b, h, w, self._totals, False)
+        return self
+
+    def reset(self):
+        """Clear the totals (no synchronisation)."""
+        if self._totals is not None:
+            self._totals.zero_()
+
+    def result(self):
+        """The totals as a dict (one device-to-host copy).  epe = epe_sum / n over all valid pixels; "1px", "3px",
+        "5px" the shares with epe < 1, 3, 5; f1 = 100 * n_outlier / n; epe_image_mean the mean over images (with
+        a valid pixel) of their mean epe; "s0-10", "s10-40", "s40+" the EPE per speed class; pixels, images,
+        nonfinite the counts.  A mean over nothing is NaN.  With nonfinite > 0 the means and f1 are NaN (a
+        non-finite prediction taints the reference's means in the same way); the shares stay counts over n."""
+        L = _lib()
+        if self._totals is None:
+            cnt, sums = [0] * L.FM_SLOTS, [0.0] * L.FM_SLOTS
+        else:
+            host = self._totals.cpu()
+            cnt, sums = host.tolist(), host.view(torch.float64).tolist()
+        c = dict(zip(L.FM_COUNTS, cnt))
+        s = {k: sums[len(L.FM_COUNTS) + i] for i, k in enumerate(L.FM_SUMS)}
+        nan = float("nan")
+        tainted = c["n_nonfinite"] > 0
+
+        def ratio(a, n, scale=1.0):
+            return scale * a / n if n > 0 else nan
+
+        def mean(a, n):
+            return nan if tainted else ratio(a, n)
+
+        n, images = c["n"], cnt[L.FM_IMAGES]
+        return {"epe": mean(s["epe_sum"], n), "1px": ratio(c["n_lt1"], n), "3px": ratio(c["n_lt3"], n),
+                "5px": ratio(c["n_lt5"], n), "f1": nan if tainted else ratio(c["n_outlier"], n, 100.0),
+                "epe_image_mean": mean(sums[L.FM_IMAGE_MEAN_SUM], images),
+                "s0-10": mean(s["epe_sum_s0_10"], c["n_s0_10"]), "s10-40": mean(s["epe_sum_s10_40"], c["n_s10_40"]),
+                "s40+": mean(s["epe_sum_s40"], c["n_s40"]), "pixels": n, "images": images,
+                "nonfinite": c["n_nonfinite"]}
