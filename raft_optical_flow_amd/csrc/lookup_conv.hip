@@ -5,21 +5,27 @@
 //   flo  = relu(convf1(flow))   7x7, 2 -> 128               core/update.py:186,205
 //
 // in ONE launch, with the 324-channel correlation rows never leaving the CU.  A work-group
-// (8 waves) owns a 2x16 tile of query pixels:
+// (16 waves, 1024 threads, one per CU: four waves per SIMD) owns a 2x16 tile of query pixels;
+// wave w owns pixels 2w and 2w + 1 (waves 8-15: the tile's second row):
 //
-//   1. every wave issues the window tiles of its four pixels (all levels, one 16-B load per
+//   1. every wave issues the window tiles of its two pixels (all levels, one 16-B load per
 //      lane each: the lookup of corr_pyramid.hip) and, behind them, the coords of convf1's
 //      8x22 flow patch;
 //   2. while they fly: the per-axis sampling entries (the reference's grid_sample arithmetic);
-//   3. per pixel: the tiles go to a double-buffered LDS patch, the lane's nine taps are
-//      interpolated and written, split into f16 hi | lo (the conv precision's operand format),
-//      straight into the convc1 A operand in LDS (32 rows x 352 K); meanwhile the flow patch
-//      becomes convf1's im2col A operand (32 rows x 128 K);
-//   4. both convs on MFMA: each wave owns 32 of convc1's 256 outputs (and waves 0-3 32 of
-//      convf1's 128); the weights come straight from L2 into registers in MFMA-fragment order
-//      (raft_lookup_conv_pack_weight), so no two waves read the same weight bytes and no LDS
-//      ring is needed;
-//   5. epilogues: bias + relu, range guard, NHWC rows.
+//   3. per pixel, one after the other: the tiles go to the wave's LDS patch, the lane's nine
+//      taps are interpolated and written, split into f16 hi | lo (the conv precision's operand
+//      format), straight into the convc1 A operand in LDS (32 rows x 352 K); meanwhile the flow
+//      patch becomes convf1's im2col A operand (32 rows x 128 K).  The chain coords -> window
+//      loads -> patch -> taps is latency, not issue: the SIMD's other three waves fill it (until
+//      round 7 a wave walked it for four pixels, two interleaved, with one other wave beside it);
+//   4. both convs on MFMA (v_mfma_f32_16x16x32, the weights as the first operand): each wave owns
+//      16 of convc1's 256 outputs over both 16-row halves of the A operand (and waves 0-7 16 of
+//      convf1's 128), within 128 VGPRs; the weights come straight from L2 into registers in
+//      fragment order (raft_lookup_conv_pack_weight: lane (n % 16, K quad q) of a wave reads the
+//      unit (t = 2 lo + (q & 1), lane 32 (q >> 1) + n % 32) of block (K-step, n / 32)), so no two
+//      waves read the same weight bytes and no LDS ring is needed;
+//   5. epilogues: bias + relu, range guard, NHWC rows (a lane holds four consecutive outputs of
+//      one pixel: one 16-B store).
 //
 // Before (round 2): the lookup + convf1 launch wrote 9.1 MB of correlation rows per iteration
 // at B=1 and convc1 (its own halo-conv launch) read them back.
@@ -36,20 +42,22 @@ constexpr int LC_TH = 2, LC_TW = 16, LC_M = 32;          // 2x16 query pixels pe
 constexpr int LC_R = 4, LC_L = 4, LC_RD = 9;              // RAFT-full: radius 4, 4 levels
 constexpr int LC_NTAP = LC_L * LC_RD * LC_RD;             // 324 correlation channels
 constexpr int LC_KS = (LC_NTAP + 31) / 32;                // 11 K-steps of 32 (K = 352)
-constexpr int LC_N = 256;                                 // convc1 outputs: 8 waves x 32
-constexpr int LC_F1N = 128;                               // convf1 outputs: waves 0-3 x 32
+constexpr int LC_WV = 16;                                 // waves per work-group (1024 threads)
+constexpr int LC_N = 256;                                 // convc1 outputs: 16 waves x 16
+constexpr int LC_F1N = 128;                               // convf1 outputs: waves 0-7 x 16
 constexpr int LC_F1K = 7, LC_F1KK = 49;
 constexpr int LC_F1KS = (2 * LC_F1KK + 31) / 32;          // convf1: K = 98 -> 4 K-steps (128)
 constexpr int LC_FPH = LC_TH + LC_F1K - 1, LC_FPW = LC_TW + LC_F1K - 1;  // 8 x 22 flow patch
-constexpr int LC_PX = 4;                                  // query pixels per wave
+constexpr int LC_PX = LC_M / LC_WV;                       // query pixels per wave: 2
+static_assert(LC_PX == 2 && LC_N == 16 * LC_WV && LC_F1N == 8 * LC_WV, "wave roles");
 
 // LDS (bytes)
 constexpr int LC_A_BYTES = LC_KS * LC_M * 128;                       // convc1 A operand: 45056
 constexpr int LC_A1_BYTES = LC_F1KS * LC_M * 128;                    // convf1 A operand: 16384
 constexpr int LC_FL_BYTES = LC_FPH * LC_FPW * 8;                     // flow patch: 1408
 constexpr int LC_PATCH_FLOATS = 16 * patch_rs<4>();                  // one pixel's window patch
-constexpr int LC_PATCH_BYTES = 8 * 2 * LC_PATCH_FLOATS * 4;          // two per wave: 69632
-constexpr int LC_YT_BYTES = 8 * LC_PX * LC_L * LC_RD * 16;           // y-entries: 18432
+constexpr int LC_PATCH_BYTES = LC_WV * LC_PATCH_FLOATS * 4;          // one per wave: 69632
+constexpr int LC_YT_BYTES = LC_WV * LC_PX * LC_L * LC_RD * 16;       // y-entries: 18432
 constexpr int LC_OFF_A1 = LC_A_BYTES, LC_OFF_FL = LC_OFF_A1 + LC_A1_BYTES, LC_OFF_PATCH = LC_OFF_FL + LC_FL_BYTES,
               LC_OFF_YT = LC_OFF_PATCH + LC_PATCH_BYTES, LC_LDS = LC_OFF_YT + LC_YT_BYTES;
 static_assert(LC_LDS <= 160 * 1024, "LDS budget");
@@ -115,7 +123,7 @@ __device__ __forceinline__ unsigned long long lc_real() {
 #endif
 
 template <int PREC>
-__global__ __launch_bounds__(512) void lookup_conv_kernel(LookupConvArgs g) {
+__global__ __launch_bounds__(64 * LC_WV) void lookup_conv_kernel(LookupConvArgs g) {
 #ifdef LC_STAMPS
   unsigned long long lc_t[10];
   const unsigned long long lc_r0 = lc_real();
@@ -123,7 +131,7 @@ __global__ __launch_bounds__(512) void lookup_conv_kernel(LookupConvArgs g) {
 #endif
   constexpr bool X3 = PREC == RAFT_PREC_F16X3;
   constexpr bool BF = PREC == RAFT_PREC_BF16;
-  constexpr int NT = X3 ? 4 : 2;  // weight fragments per K-step (hi qq0, hi qq1, lo qq0, lo qq1)
+  constexpr int NT = X3 ? 2 : 1;  // weight fragments per K-step (hi, lo)
   constexpr int R = LC_R, RD = LC_RD, WD = 2 * R + 2, RS = patch_rs<4>();
   __shared__ __attribute__((aligned(1024))) char smem[LC_LDS];
   const LookupArgs& a = g.a;
@@ -142,14 +150,19 @@ __global__ __launch_bounds__(512) void lookup_conv_kernel(LookupConvArgs g) {
   constexpr int LC_PF = 3;
   constexpr int PF = LC_PF;
   h8 wb[PF + 1][NT];
-  auto load_w = [&](int j, h8 (&dst)[NT]) {
-    const h8* wf = j < LC_KS ? g.wfrag + ((j * (LC_N / 32) + wv) * 4) * 64
-                             : g.f1frag + (((j - LC_KS) * (LC_F1N / 32) + wv) * 4) * 64;
+  // The wave owns outputs 16 wv .. 16 wv + 15; lane (n16, q) = (lane % 16, lane / 16) holds K quad q of output
+  // n = 16 wv + n16: the packed unit (t = 2 lo + (q & 1), lane' = 32 (q >> 1) + n % 32) of block (j, n / 32)
+  const int n16 = lane & 15, q4 = lane >> 4;
+  const int wlane = (q4 & 1) * 64 + 32 * (q4 >> 1) + 16 * (wv & 1) + n16;
+  auto load_w = [&](int j, h8 (&dst)[NT]) {  // (waves 8-15: convf1's steps of wave 7, unused)
+    const int f1s = wv < LC_F1N / 16 ? wv >> 1 : LC_F1N / 32 - 1;
+    const h8* wf = j < LC_KS ? g.wfrag + ((j * (LC_N / 32) + (wv >> 1)) * 4) * 64
+                             : g.f1frag + (((j - LC_KS) * (LC_F1N / 32) + f1s) * 4) * 64;
 #pragma unroll
-    for (int t = 0; t < NT; ++t) dst[t] = wf[t * 64 + lane];
+    for (int t = 0; t < NT; ++t) dst[t] = wf[t * 128 + wlane];
   };
 
-  // ---- 1. the window tiles of this wave's four query pixels (the critical path) --------------
+  // ---- 1. the window tiles of this wave's two query pixels (the critical path) ---------------
   const int ti = lane >> 4, tj = (lane >> 2) & 3, rr = lane & 3;
   const int lrow = ti * 4 + rr;
   // per-level map geometry in registers up front (re-read from the kernel arguments inside the
@@ -167,7 +180,7 @@ __global__ __launch_bounds__(512) void lookup_conv_kernel(LookupConvArgs g) {
   float px_x[LC_PX], px_y[LC_PX];
   int px_gp[LC_PX];
   bool px_ok[LC_PX];
-  // the four pixels' coords, every load issued before the first is used (uniform: scalar loads)
+  // the two pixels' coords
 #pragma unroll
   for (int k = 0; k < LC_PX; ++k) {
     const int mk = LC_PX * wv + k;
@@ -177,10 +190,10 @@ __global__ __launch_bounds__(512) void lookup_conv_kernel(LookupConvArgs g) {
     px_gp[k] = ok ? b * P + yy * W + xx : b * P;
   }
   {
-    // one round trip: lane k < 4 loads pixel k's x and y (two 4-B loads), then lane reads
+    // one round trip: lane k < 2 loads pixel k's x and y (two 4-B loads), then lane reads
     int gk = px_gp[0];
 #pragma unroll
-    for (int k = 1; k < LC_PX; ++k) gk = (lane & 3) == k ? px_gp[k] : gk;
+    for (int k = 1; k < LC_PX; ++k) gk = (lane & (LC_PX - 1)) == k ? px_gp[k] : gk;
     const float cx = a.coords[2L * gk], cy = a.coords[2L * gk + 1];
 #pragma unroll
     for (int k = 0; k < LC_PX; ++k) {
@@ -206,19 +219,16 @@ __global__ __launch_bounds__(512) void lookup_conv_kernel(LookupConvArgs g) {
   const bool fin = fi < LC_FPH * LC_FPW && (unsigned)fyy < (unsigned)H && (unsigned)fxx < (unsigned)W;
   f32x2 fc = {0.f, 0.f};
   if (fin) fc = *reinterpret_cast<const f32x2*>(a.coords + 2L * ((long)b * P + fyy * W + fxx));
-  const int m = lane & 31, h = lane >> 5;
-  const float c1b = g.bias ? g.bias[32 * wv + m] : 0.f;
-  const float f1b = (wv < 4 && g.f1bias) ? g.f1bias[32 * wv + m] : 0.f;
   // (their waits here, behind the coords' round trip: after the window loads the compiler, which
   // cannot count the loads of the two window paths below as equal, would wait for all of them)
-  asm volatile("" ::"v"(prm), "v"(c1b), "v"(f1b), "v"(fc));
+  asm volatile("" ::"v"(prm), "v"(fc));
 
   __builtin_amdgcn_sched_barrier(0);
   f32x4 v[LC_PX][LC_L];
   // Every level's maps within 2^31 bytes (uniform): one buffer resource per level and 32-bit byte
   // offsets, the window test per lane on the VALU.  Per (pixel, level) the scalar unit then computes
   // only the window origin and one product (~12 SALU instead of ~46 with a 64-bit base and a resource
-  // per window: the scalar unit, shared by the CU's 8 waves, was the tile-issue phase's limit).
+  // per window: the scalar unit, shared by the CU's waves, was the tile-issue phase's limit).
   bool off32 = true;
   const unsigned nmaps = (unsigned)(a.B * P);
 #pragma unroll
@@ -233,13 +243,13 @@ __global__ __launch_bounds__(512) void lookup_conv_kernel(LookupConvArgs g) {
       lano[l] = __umul24((unsigned)ti, (unsigned)(64 * ltw[l])) + 16u * (unsigned)(lane & 15);
       lmsz4[l] = lmsz[l] * 4u;
     }
-    // The 16 (pixel, level) windows' parameters computed once, window (k, l) on lane 4k + l, on the VALU,
+    // The 8 (pixel, level) windows' parameters computed once, window (k, l) on lane 4k + l, on the VALU,
     // and read back per load (3 v_readlane): the window's origin offset and its row / tile-column
     // intervals clipped to the map (relative to the lane's row / column in the window, 16 + 16 bits).
-    // The per-load scalar chain (~19 SALU on the unit the CU's 8 waves share) becomes ~4.
+    // The per-load scalar chain (~19 SALU on the unit the CU's waves share) becomes ~4.
     int t_sb, t_row, t_col;
     {
-      const int ik = (lane >> 2) & 3, il = lane & 3;
+      const int ik = (lane >> 2) & (LC_PX - 1), il = lane & 3;
       float fx = px_x[0], fy = px_y[0];
       int gpk = px_gp[0];
       bool okk = px_ok[0];
@@ -289,7 +299,7 @@ __global__ __launch_bounds__(512) void lookup_conv_kernel(LookupConvArgs g) {
     // window as before)
     int t_lo, t_hi, t_row, t_col;
     {
-      const int ik = (lane >> 2) & 3, il = lane & 3;
+      const int ik = (lane >> 2) & (LC_PX - 1), il = lane & 3;
       float fx = px_x[0], fy = px_y[0];
       int gpk = px_gp[0];
       bool okk = px_ok[0];
@@ -343,7 +353,7 @@ __global__ __launch_bounds__(512) void lookup_conv_kernel(LookupConvArgs g) {
     }
   }
   LC_STAMP(1);
-  // ---- 2. while the tiles fly: the per-axis sampling entries of the four pixels ------------
+  // ---- 2. while the tiles fly: the per-axis sampling entries of the two pixels -------------
   // lane (l, ix) = (lane / 9, lane % 9), lanes 0 .. 35: x-entry ix kept in registers, y-entry
   // ix through LDS (the reference's arithmetic, see axis_entry)
   int4* ytab = reinterpret_cast<int4*>(smem + LC_OFF_YT) + wv * LC_PX * LC_L * RD;
@@ -375,20 +385,17 @@ __global__ __launch_bounds__(512) void lookup_conv_kernel(LookupConvArgs g) {
   LC_STAMP(2);
 
   // ---- 3. the taps of each pixel -> split rows of convc1's A operand ------------------------
-  // (the first PF K-steps of the weight stream are issued here, behind the tiles, so they
-  // land during the taps)
-#pragma unroll
-  for (int j = 0; j < PF; ++j) load_w(j, wb[j]);
+  // (the first PF K-steps of the weight stream are issued before the last pixel's round, so they land
+  // during its taps and the barriers; before the first round they would hold 24 VGPRs beside both
+  // pixels' windows)
   char* Abase = smem;
   bool big = false;
-  auto patch_of = [&](int k) {
-    return reinterpret_cast<float*>(smem + LC_OFF_PATCH) + (wv * 2 + (k & 1)) * LC_PATCH_FLOATS;
-  };
+  float* const wpatch = reinterpret_cast<float*>(smem + LC_OFF_PATCH) + wv * LC_PATCH_FLOATS;  // the wave's patch
   // this lane's nine output channels c = l*81 + ix*9 + iy
   const int cbase = l * RD * RD + ix * RD;
-  // the nine taps of pixel k from its staged patch
+  // the nine taps of pixel k from the staged patch
   auto taps = [&](int k, float (&val)[RD]) {
-    const float* patch = patch_of(k);
+    const float* patch = wpatch;
     const int4* yt = ytab + k * LC_L * RD;
     const float ex = 1.0f - xt[k];
     const int xwk = xw[k];
@@ -453,6 +460,8 @@ __global__ __launch_bounds__(512) void lookup_conv_kernel(LookupConvArgs g) {
                          patch[pidx<4>(r0 + 1, c0, l)] * (ty * ex) + patch[pidx<4>(r0 + 1, c0 + 1, l)] * (ty * xt[k]);
         val[iy] = nan ? __builtin_nanf("") : vv;
         deferred |= (!on && !nan) ? 1u << iy : 0u;
+        // (the rare path one tap at a time: interleaved, its nine taps' corners and indices spilled at 128 VGPRs)
+        __builtin_amdgcn_sched_barrier(0);
       }
       if (deferred != 0) {
         // taps whose floor the float round trip moved off the staged patch: the four
@@ -525,88 +534,94 @@ __global__ __launch_bounds__(512) void lookup_conv_kernel(LookupConvArgs g) {
       a.flow[(long)px_gp[k] * a.flow_ld + lane] = (lane == 0 ? px_x[k] : px_y[k]) - gcoord;
     }
   };
-  // two pixels per round: both patches staged, one wave sync, both pixels' taps interleaved
+  // one pixel per round through the wave's one patch (the SIMD's other three waves fill its waits)
 #pragma unroll
-  for (int k = 0; k < LC_PX; k += 2) {
+  for (int k = 0; k < LC_PX; ++k) {
+    if (k == LC_PX - 1) {
 #pragma unroll
-    for (int lv_ = 0; lv_ < LC_L; ++lv_) {
-      *reinterpret_cast<f32x4*>(&patch_of(k)[pidx<4>(lrow, tj * 4, lv_)]) = v[k][lv_];
-      *reinterpret_cast<f32x4*>(&patch_of(k + 1)[pidx<4>(lrow, tj * 4, lv_)]) = v[k + 1][lv_];
+      for (int j = 0; j < PF; ++j) load_w(j, wb[j]);
     }
+#pragma unroll
+    for (int lv_ = 0; lv_ < LC_L; ++lv_) *reinterpret_cast<f32x4*>(&wpatch[pidx<4>(lrow, tj * 4, lv_)]) = v[k][lv_];
     wave_sync();
-    float va[RD], vb[RD];
+    float va[RD];
     taps(k, va);
-    taps(k + 1, vb);
     write_row(k, va);
-    write_row(k + 1, vb);
-    wave_sync();  // (the patches are read before the next round overwrites them)
+    wave_sync();  // (the patch is read before the next round overwrites it)
   }
   if (a.range_flag && big) *a.range_flag = 1;
+  // the biases of the lane's four outputs of step 5 (channels 16 wv + 4 q4 .. + 3), issued here behind the
+  // first weight steps: they land under the barriers and the K stream (earlier they cost the taps 8 VGPRs)
+  float c1b[4], f1b[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    c1b[i] = g.bias ? g.bias[16 * wv + 4 * q4 + i] : 0.f;
+    f1b[i] = (wv < LC_F1N / 16 && g.f1bias) ? g.f1bias[16 * wv + 4 * q4 + i] : 0.f;
+  }
   LC_STAMP(3);
   __syncthreads();  // the flow patch is visible
-  // convf1's im2col A operand: row mm, K = 2 (dy*7 + dx) + ci (the GATHER packing), 8 K per thread
+  // convf1's im2col A operand: row mm, K = 2 (dy*7 + dx) + ci (the GATHER packing), 4 K per thread
   {
-    const int mm = threadIdx.x >> 4, q = threadIdx.x & 15;
+    const int mm = threadIdx.x >> 5, q = threadIdx.x & 31;
     const int py = mm >> 4, px = mm & 15;
-    float e[8];
+    float e[4];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int k = 8 * q + i, t = k >> 1;
+    for (int i = 0; i < 4; ++i) {
+      const int k = 4 * q + i, t = k >> 1;
       const int dy = t / LC_F1K, dx = t - dy * LC_F1K;
       const float2 fv = fl[(py + (k < 2 * LC_F1KK ? dy : 0)) * LC_FPW + px + (k < 2 * LC_F1KK ? dx : 0)];
       e[i] = k < 2 * LC_F1KK ? ((k & 1) ? fv.y : fv.x) : 0.f;
     }
+    // (split8 of the four values: the lower half of its result, the same bytes as before)
     h8 hi, lo;
-    split8<X3, BF>(f32x4{e[0], e[1], e[2], e[3]}, f32x4{e[4], e[5], e[6], e[7]}, hi, lo);
-    const int j = q >> 2, qd = q & 3, sw = (mm >> 1) & 7;
-    char* row = smem + LC_OFF_A1 + j * (LC_M * 128) + mm * 128;
-    *reinterpret_cast<h8*>(row + ((qd ^ sw) << 4)) = hi;
-    if constexpr (X3) *reinterpret_cast<h8*>(row + (((4 + qd) ^ sw) << 4)) = lo;
+    split8<X3, BF>(f32x4{e[0], e[1], e[2], e[3]}, f32x4{0.f, 0.f, 0.f, 0.f}, hi, lo);
+    const int j = q >> 3, qd = (q >> 1) & 3, sw = (mm >> 1) & 7;
+    char* row = smem + LC_OFF_A1 + j * (LC_M * 128) + mm * 128 + 8 * (q & 1);
+    *reinterpret_cast<h4*>(row + ((qd ^ sw) << 4)) = h4{hi[0], hi[1], hi[2], hi[3]};
+    if constexpr (X3) *reinterpret_cast<h4*>(row + (((4 + qd) ^ sw) << 4)) = h4{lo[0], lo[1], lo[2], lo[3]};
   }
   __syncthreads();  // every A row is in LDS
   LC_STAMP(4);
 
-  // ---- 4. convc1 (all waves, 32 outputs each) then convf1 (waves 0-3) on MFMA: one K stream ----
-  const int sw = (m >> 1) & 7;
-  f32x16 acc = {}, accx = {}, facc = {}, faccx = {};
-  const bool f1w = wv < LC_F1N / 32;  // (wave-uniform)
+  // ---- 4. convc1 (all waves, 16 outputs each) then convf1 (waves 0-7) on MFMA: one K stream ----
+  // v_mfma_f32_16x16x32 with the weights as its first operand (16 outputs x 32 K) and a 16-row half of the A
+  // operand as its second (32 K x 16 pixels), once per half: lane (n16, q4) holds K quad q4 of output 16 wv + n16
+  // and of pixel 16 r + n16, and four consecutive outputs 16 wv + 4 q4 .. + 3 of pixel 16 r + n16 of the result.
+  f32x4 acc[2] = {}, accx[2] = {}, facc[2] = {}, faccx[2] = {};
+  const bool f1w = wv < LC_F1N / 16;  // (wave-uniform)
   // The K stream with its schedule pinned (one scheduling region per K-step): the weight loads of step
   // j + PF first, then the A fragments of step j + 1 from LDS one per MFMA gap beside step j's MFMAs.  Left
   // to itself the compiler sank both to just before their use (a vmcnt / lgkmcnt wait per MFMA pair: the L2
   // round trip of every weight K-step exposed).  Every statement is unconditional so a step is one basic
-  // block: waves 4-7 load convf1's weight addresses of wave 3 and read its A operand without using them.
+  // block: waves 8-15 load convf1's weight addresses of wave 7 and read its A operand without using them.
   struct AF {
-    h8 ah[2], al[2];
+    h8 ah[2], al[2];  // per 16-row half
   };
+  const int arow = n16 * 128, asw = (n16 >> 1) & 7;  // (row 16 r + n16: swizzle ((16 r + n16) >> 1) & 7 = asw)
   auto read_af = [&](const char* A, AF& f) {
-    const char* row = A + m * 128;
 #pragma unroll
-    for (int qq = 0; qq < 2; ++qq) {
-      f.ah[qq] = *reinterpret_cast<const h8*>(row + (((2 * h + qq) ^ sw) << 4));
-      if constexpr (X3) f.al[qq] = *reinterpret_cast<const h8*>(row + (((4 + 2 * h + qq) ^ sw) << 4));
+    for (int r = 0; r < 2; ++r) {
+      const char* row = A + r * (16 * 128) + arow;
+      f.ah[r] = *reinterpret_cast<const h8*>(row + ((q4 ^ asw) << 4));
+      if constexpr (X3) f.al[r] = *reinterpret_cast<const h8*>(row + (((4 + q4) ^ asw) << 4));
     }
   };
-  auto mfma_af = [&](const AF& f, const h8 (&B)[NT], f32x16& c, f32x16& cx) {
-#pragma unroll
-    for (int qq = 0; qq < 2; ++qq) {
-      if constexpr (BF) {
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf8, f.ah[qq]), __builtin_bit_cast(bf8, B[qq]),
-                                                    c, 0, 0, 0);
-      } else {
-        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.ah[qq], B[qq], c, 0, 0, 0);
-      }
-      if constexpr (X3) {
-        cx = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.ah[qq], B[2 + qq], cx, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.al[qq], B[qq], c, 0, 0, 0);
-      }
-    }
+  auto mfma1 = [&](const h8& w, const h8& x, f32x4& c) {
+    if constexpr (BF)
+      c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf8, w), __builtin_bit_cast(bf8, x), c, 0, 0, 0);
+    else
+      c = __builtin_amdgcn_mfma_f32_16x16x32_f16(w, x, c, 0, 0, 0);
   };
-  auto load_w_any = [&](int j, h8 (&dst)[NT]) {  // (waves 4-7: convf1's steps of wave 3, unused)
-    const int wq = j < LC_KS ? wv : (wv < LC_F1N / 32 ? wv : LC_F1N / 32 - 1);
-    const h8* wf = j < LC_KS ? g.wfrag + ((j * (LC_N / 32) + wq) * 4) * 64
-                             : g.f1frag + (((j - LC_KS) * (LC_F1N / 32) + wq) * 4) * 64;
-#pragma unroll
-    for (int t = 0; t < NT; ++t) dst[t] = wf[t * 64 + lane];
+  // (per accumulator the order of the three products is the split's: hi*hi, then lo*hi; hi*lo on its own chain)
+  auto mfma_af = [&](const AF& f, const h8 (&B)[NT], f32x4 (&c)[2], f32x4 (&cx)[2]) {
+    mfma1(B[0], f.ah[0], c[0]);
+    mfma1(B[0], f.ah[1], c[1]);
+    if constexpr (X3) {
+      mfma1(B[NT - 1], f.ah[0], cx[0]);
+      mfma1(B[NT - 1], f.ah[1], cx[1]);
+      mfma1(B[0], f.al[0], c[0]);
+      mfma1(B[0], f.al[1], c[1]);
+    }
   };
   constexpr int NRA = X3 ? 4 : 2, NMA = X3 ? 6 : 2;
   auto groups = [&](bool loads) {
@@ -622,7 +637,7 @@ __global__ __launch_bounds__(512) void lookup_conv_kernel(LookupConvArgs g) {
 #pragma unroll
   for (int j = 0; j < LC_KS; ++j) {
     __builtin_amdgcn_sched_barrier(0);
-    if (j + PF < LC_KS + LC_F1KS) load_w_any(j + PF, wb[(j + PF) % (PF + 1)]);
+    if (j + PF < LC_KS + LC_F1KS) load_w(j + PF, wb[(j + PF) % (PF + 1)]);
     read_af(j + 1 < LC_KS ? Abase + (j + 1) * (LC_M * 128) : smem + LC_OFF_A1, af[(j + 1) & 1]);
     mfma_af(af[j & 1], wb[j % (PF + 1)], acc, accx);
     groups(j + PF < LC_KS + LC_F1KS);
@@ -632,7 +647,7 @@ __global__ __launch_bounds__(512) void lookup_conv_kernel(LookupConvArgs g) {
 #pragma unroll
     for (int j = LC_KS; j < LC_KS + LC_F1KS; ++j) {
       __builtin_amdgcn_sched_barrier(0);
-      if (j + PF < LC_KS + LC_F1KS) load_w_any(j + PF, wb[(j + PF) % (PF + 1)]);
+      if (j + PF < LC_KS + LC_F1KS) load_w(j + PF, wb[(j + PF) % (PF + 1)]);
       if (j + 1 < LC_KS + LC_F1KS) read_af(smem + LC_OFF_A1 + (j + 1 - LC_KS) * (LC_M * 128), af[(j + 1) & 1]);
       mfma_af(af[j & 1], wb[j % (PF + 1)], facc, faccx);
       __builtin_amdgcn_sched_barrier(0);
@@ -640,33 +655,43 @@ __global__ __launch_bounds__(512) void lookup_conv_kernel(LookupConvArgs g) {
   }
   if constexpr (X3) {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
+    for (int r = 0; r < 2; ++r) {
       acc[r] += accx[r] * (1.0f / SPLIT_SCALE);
       facc[r] += faccx[r] * (1.0f / SPLIT_SCALE);
     }
   }
 #ifdef LC_STAMPS
-  asm volatile("" ::"v"(acc[0]), "v"(acc[15]), "v"(facc[0]));
+  asm volatile("" ::"v"(acc[0]), "v"(acc[1]), "v"(facc[0]));
 #endif
   LC_STAMP(5);
 
   // ---- 5. epilogues: bias, relu, range guard, NHWC rows ----------------------------------------
-  auto store = [&](const f32x16& c, float bias, float* out, int ld, int n, int* flag) {
+  // the lane's four consecutive outputs of pixel 16 r + n16: one 16-B store where the rows allow it
+  auto store = [&](const f32x4 (&c)[2], const float (&bias)[4], float* out, int ld, int n, int* flag) {
     bool obig = false;
+    const bool vec = ((ld & 3) | (int)(reinterpret_cast<uintptr_t>(out) & 15)) == 0;  // (uniform)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int mm = (r & 3) + 8 * (r >> 2) + 4 * h;
-      const int yy = y0 + (mm >> 4), xx = x0 + (mm & 15);
-      const float o = fmaxf(c[r] + bias, 0.f);
+    for (int r = 0; r < 2; ++r) {
+      const int yy = y0 + r, xx = x0 + n16;
+      f32x4 o;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) o[i] = fmaxf(c[r][i] + bias[i], 0.f);
       if (yy < H && xx < W) {
-        obig |= o > RAFT_RANGE_LIMIT;
-        out[((long)b * P + yy * W + xx) * ld + n] = o;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) obig |= o[i] > RAFT_RANGE_LIMIT;
+        float* dst = out + ((long)b * P + yy * W + xx) * ld + n;
+        if (vec) {
+          *reinterpret_cast<f32x4*>(dst) = o;
+        } else {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) dst[i] = o[i];
+        }
       }
     }
     if (flag && obig) *flag = 1;
   };
-  store(acc, c1b, g.out, g.out_ld, 32 * wv + m, g.out_flag);
-  if (wv < LC_F1N / 32) store(facc, f1b, g.f1out, g.f1out_ld, 32 * wv + m, g.f1flag);
+  store(acc, c1b, g.out, g.out_ld, 16 * wv + 4 * q4, g.out_flag);
+  if (f1w) store(facc, f1b, g.f1out, g.f1out_ld, 16 * wv + 4 * q4, g.f1flag);
   if (g.span_slot >= 0) {  // (uniform) the work-group's end once its stores have completed
     __builtin_amdgcn_s_waitcnt(0);
     __syncthreads();
@@ -677,7 +702,7 @@ __global__ __launch_bounds__(512) void lookup_conv_kernel(LookupConvArgs g) {
   __builtin_amdgcn_s_waitcnt(0);
   LC_STAMP(6);
   const unsigned long long lc_r1 = lc_real();
-  const unsigned wid = blockIdx.x * 8 + wv;
+  const unsigned wid = blockIdx.x * LC_WV + wv;
   if (lane == 0 && wid < 16384) {
     unsigned long long* gs = g_lcstamp + wid * 16;
     gs[0] = lc_r0;
@@ -771,11 +796,11 @@ extern "C" int raft_corr_lookup_conv(const float* pyramid, int B, int H, int W, 
   hipStream_t s = as_stream(stream);
   const dim3 grid((unsigned)nt);
   if (precision == RAFT_PREC_F16X3)
-    hipLaunchKernelGGL(lookup_conv_kernel<RAFT_PREC_F16X3>, grid, dim3(512), 0, s, g);
+    hipLaunchKernelGGL(lookup_conv_kernel<RAFT_PREC_F16X3>, grid, dim3(64 * LC_WV), 0, s, g);
   else if (precision == RAFT_PREC_F16)
-    hipLaunchKernelGGL(lookup_conv_kernel<RAFT_PREC_F16>, grid, dim3(512), 0, s, g);
+    hipLaunchKernelGGL(lookup_conv_kernel<RAFT_PREC_F16>, grid, dim3(64 * LC_WV), 0, s, g);
   else
-    hipLaunchKernelGGL(lookup_conv_kernel<RAFT_PREC_BF16>, grid, dim3(512), 0, s, g);
+    hipLaunchKernelGGL(lookup_conv_kernel<RAFT_PREC_BF16>, grid, dim3(64 * LC_WV), 0, s, g);
   return check_launch("raft_corr_lookup_conv");
 }
 

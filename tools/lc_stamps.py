@@ -43,14 +43,14 @@ for rep in range(3):
     torch.cuda.synchronize()
     lk[-1](K.stream_handle())
     torch.cuda.synchronize()
-nwg = 2048
-buf = np.zeros(nwg * 8 * 16, dtype=np.uint64)
+nwg, wpg = 1024, 16  # work-groups stamped at most, waves per work-group (LC_WV)
+buf = np.zeros(nwg * wpg * 16, dtype=np.uint64)
 lib.raft_debug_lcstamps(buf.ctypes.data, buf.size)
-s = buf.reshape(nwg * 8, 16).astype(np.int64)
+s = buf.reshape(nwg * wpg, 16).astype(np.int64)
 s = s[s[:, 1] > 0]
 print(f"  {s.shape[0]} waves stamped")
 r0, r1, t = s[:, 0], s[:, 1], s[:, 2:9]
-names = ["issue loads", "axis entries + flow patch", "taps x4 (tile wait incl.)", "sync + convf1 A + sync",
+names = ["issue loads", "axis entries + flow patch", "taps x2 (tile wait incl.)", "sync + convf1 A + sync",
          "GEMMs", "epilogues"]
 d = np.diff(t, axis=1)
 for k, n in enumerate(names):
