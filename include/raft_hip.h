@@ -878,6 +878,97 @@ int raft_flow_metrics(const float* flow, long flow_batch_stride, long flow_chan_
                       int W, float gt_limit, void* record, void* totals, float* epe_map, void* ws,
                       raft_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * Scoring a flow without ground truth (utils.photo_errors, utils.PhotoMetrics): the data term of the
+ * unsupervised flow literature.  Frame 2 is warped back by the flow and compared with frame 1,
+ * photometrically and under the soft census transform, over the pixels that are neither masked out nor
+ * pushed out of the frame: what the reference's photometric_loss, ternary_loss (unflow_loss_pytorch.py) and
+ * census_loss (uflow_loss_pytorch.py) compute from a grid_sample, two 49-channel convolutions and a dozen
+ * elementwise passes.  Additive entries: RAFT_HIP_ABI_VERSION stays 19.
+ * --------------------------------------------------------------------------- */
+/* Definition.  I1, I2 are the two frames in 0..255 units, P = patch in {3, 5, 7}, r = P / 2.  Every value
+ * is IEEE fp32, every operation rounded to nearest and nothing fused, unless said otherwise.
+ *   W2_c(x)   raft_warp_frame(I2, flow, zeros mode)'s float32 value of channel c at x, bit for bit: the same
+ *             taps, blend and valid(x); a flow that is not finite or >= 2^30 gives 0 and valid = 0.
+ *   g1, g2    the grey values (I1_0 + I1_1 + I1_2) / 3 and (W2_0 + W2_1 + W2_2) / 3, summed left to right.
+ *   census    for each of the P * P offsets o in row-major order (dy outer, dx inner), d = g(x + o) - g(x)
+ *             with g(x + o) = 0 where x + o lies outside the H x W frame (the reference's 'same' zero
+ *             padding), c_o = d / sqrt(0.81f + d * d).
+ *   h(x)      the soft Hamming distance: the sum over o, in that order, of q_o / (0.1f + q_o) with
+ *             q_o = (c1_o - c2_o)^2; 0 <= h <= P * P.
+ *   e_c(x)    I1_c(x) - W2_c(x), the photometric residual of channel c.
+ * Which pixels count:
+ *   m(x)      the mask says so (mask == NULL: every pixel; RAFT_MASK_U8 != 0; RAFT_MASK_F32 >= 0.5f, a NaN
+ *             fails) AND, with RAFT_PHOTO_OUTGOING, valid(x) (the reference's create_outgoing_mask).
+ *   int(x)    r <= x < W - r and r <= y < H - r (zero_mask_border / create_mask).  H or W smaller than P
+ *             is legal: no pixel is interior.
+ *   finite(x) h(x) and the three squares e_c * e_c are finite.
+ * Record.  RAFT_PHOTO_METRICS_SLOTS = 16 slots of 64 bits per sample, int64 counts first, fp64 sums (stored
+ * by their bits) after:
+ *   RAFT_PM_N_MASK        pixels with m
+ *   RAFT_PM_N_CENSUS      pixels with m and int
+ *   RAFT_PM_N_VALID       pixels with valid, whatever the mask and the flags
+ *   RAFT_PM_N_NONFINITE   pixels with m and not finite: counted in N_MASK / N_CENSUS and in no sum
+ *   RAFT_PM_PIXELS        H * W
+ *   RAFT_PM_L1_SUM        over m and finite, over c: |e_c|
+ *   RAFT_PM_PHOTO_SUM     over m and finite, over c: powf(e_c * e_c + 1e-6f, 0.45f)  (photometric_loss:
+ *                         charbonnier(beta = 255) on 0..1 images, in 0..255 units)
+ *   RAFT_PM_HAMMING_SUM   over m, int and finite: h
+ *   RAFT_PM_CENSUS_SUM    over m, int and finite: powf(h + 0.01f, 0.4f)  (abs_robust_loss: census_loss's
+ *                         numerator)
+ *   RAFT_PM_TERNARY_SUM   over m, int and finite: powf(h * h + 1e-6f, 0.45f)  (ternary_loss's numerator)
+ * each term an fp32 value, widened and added in fp64.  `totals`, if given, is one record that the call ADDS
+ * every sample's record into (zero it before the first call), together with
+ *   RAFT_PM_IMAGES                  the number of samples with N_CENSUS > 0
+ *   RAFT_PM_IMAGE_CENSUS_MEAN_SUM   the fp64 sum of CENSUS_SUM / N_CENSUS over those samples
+ * which are 0 in a sample's record, as are the reserved slots 12 .. 15 (written as 0).
+ * census_map, if given: float32 [B][H][W] dense, h(x) at every pixel, whatever the mask, border pixels
+ * included (with their zero-padded neighbours): the per-pixel confidence image.
+ *
+ * Launches.  Two, no atomics.  The tile kernel: a work-group of 256 threads owns tiles of
+ * RAFT_PHOTO_METRICS_TILE_H x RAFT_PHOTO_METRICS_TILE_W pixels of one sample (a thread 4 rows of one column);
+ * it fills g1 and g2 of the tile and its halo of r pixels into LDS, walks the P * P offsets from there, sums
+ * in integers and fp64 per thread, by a butterfly per wave, through LDS in wave order per work-group, and
+ * writes one partial record to ws.  NB = min(tiles, RAFT_PHOTO_METRICS_MAX_BLOCKS) work-groups per sample,
+ * work-group p taking tiles p, p + NB, ...: a function of (H, W) only, never of the device.  The finalize
+ * kernel: one work-group adds the partials in index order, writes the records and adds them into the totals
+ * in sample order.  Two runs are bitwise equal, and a sample's record does not depend on its batch index.
+ *
+ * Layout.  frame1 and frame2 share frame_dtype: RAFT_FRAME_F32_NCHW, element (b, c, y, x) at
+ * p[b * batch_stride + c * chan_stride + y * pitch + x] (strides in floats, each frame its own, pitch >= W;
+ * a crop is read in place by passing its first element), or RAFT_FRAME_U8_NHWC, uint8 [B][H][W][3] dense
+ * (the strides are not read).  Three channels.  flow as raft_flow_metrics takes it; mask [B][H][W] with a
+ * batch stride and a pitch in elements, or NULL.  record [B][16], totals [16] or NULL, ws of
+ * raft_photo_metrics_ws_bytes(B, H, W, patch) bytes (no initialisation needed): 8-byte aligned; float32
+ * frames, flow, a float32 mask and census_map 4-byte.  No output aliases an input or another output.
+ * B * H * W < 2^30. */
+#define RAFT_PHOTO_METRICS_SLOTS 16
+#define RAFT_PHOTO_METRICS_TILE_H 16
+#define RAFT_PHOTO_METRICS_TILE_W 64
+#define RAFT_PHOTO_METRICS_MAX_BLOCKS 512 /* work-groups per sample at most; larger samples wrap */
+#define RAFT_PHOTO_OUTGOING 1             /* flags bit 0: pixels whose target leaves the frame do not count */
+#define RAFT_PM_N_MASK 0
+#define RAFT_PM_N_CENSUS 1
+#define RAFT_PM_N_VALID 2
+#define RAFT_PM_N_NONFINITE 3
+#define RAFT_PM_PIXELS 4
+#define RAFT_PM_L1_SUM 5
+#define RAFT_PM_PHOTO_SUM 6
+#define RAFT_PM_HAMMING_SUM 7
+#define RAFT_PM_CENSUS_SUM 8
+#define RAFT_PM_TERNARY_SUM 9
+#define RAFT_PM_IMAGES 10
+#define RAFT_PM_IMAGE_CENSUS_MEAN_SUM 11
+#define RAFT_PM_RESERVED 12 /* 12 .. 15 */
+/* bytes of raft_photo_metrics' workspace; 0 for sizes (or a patch) it rejects */
+size_t raft_photo_metrics_ws_bytes(int B, int H, int W, int patch);
+int raft_photo_metrics(const void* frame1, long f1_batch_stride, long f1_chan_stride, long f1_pitch,
+                       const void* frame2, long f2_batch_stride, long f2_chan_stride, long f2_pitch, int frame_dtype,
+                       const float* flow, long flow_batch_stride, long flow_chan_stride, long flow_pitch,
+                       const void* mask, int mask_dtype, long mask_batch_stride, long mask_pitch, int B, int H, int W,
+                       int patch, int flags, void* record, void* totals, float* census_map, void* ws,
+                       raft_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

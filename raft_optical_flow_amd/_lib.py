@@ -55,6 +55,19 @@ FM_IMAGES = 13
 FM_IMAGE_MEAN_SUM = 14
 FM_RESERVED = 15
 
+# raft_photo_metrics: the record's slots (RAFT_PM_*), int64 counts then fp64 sums, the flag and the launch constants
+PM_SLOTS = 16
+PM_TILE_H = 16        # RAFT_PHOTO_METRICS_TILE_H / _TILE_W: the tile a work-group takes per pass
+PM_TILE_W = 64
+PM_MAX_BLOCKS = 512   # work-groups per sample at most; samples with more tiles wrap
+PM_PATCHES = (3, 5, 7)
+PM_OUTGOING = 1       # flags bit 0: pixels whose target leaves the frame do not count
+PM_COUNTS = ("n_mask", "n_census", "n_valid", "n_nonfinite", "pixels")
+PM_SUMS = ("l1_sum", "photo_sum", "hamming_sum", "census_sum", "ternary_sum")
+PM_IMAGES = 10
+PM_IMAGE_CENSUS_MEAN_SUM = 11
+PM_RESERVED = 12      # 12 .. 15
+
 EPI_LINEAR = 0
 EPI_RELU = 1
 EPI_RESID_RELU = 2
@@ -226,6 +239,10 @@ _PROTOS = {
     "raft_flow_metrics_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "raft_flow_metrics": (c_int, [P, c_long, c_long, c_long, P, c_long, c_long, c_long, P, c_int, c_long, c_long,
                                   c_int, c_int, c_int, c_float, P, P, P, P, P]),
+    "raft_photo_metrics_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "raft_photo_metrics": (c_int, [P, c_long, c_long, c_long, P, c_long, c_long, c_long, c_int, P, c_long, c_long,
+                                   c_long, P, c_int, c_long, c_long, c_int, c_int, c_int, c_int, c_int, P, P, P, P,
+                                   P]),
 }
 
 EXPORTED = tuple(_PROTOS)

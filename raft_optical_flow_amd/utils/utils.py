@@ -28,6 +28,14 @@
                                                    a synchronisation per pair: validate_chairs reads "epe",
                                                    validate_sintel "epe", "1px", "3px", "5px", validate_kitti
                                                    "epe_image_mean" and "f1"
+  photo_errors         unflow_loss_pytorch.py:247,  per-sample label-free scores of a flow (raft_photo_metrics): frame
+                       :411, :612, :694             2 warped back by the flow against frame 1, photometrically and
+                       uflow_loss_pytorch.py:609,   under the soft census transform, over the pixels that are neither
+                       :880-944                     masked out nor pushed out of the frame: the sums of
+                                                   photometric_loss, ternary_loss and census_loss (census_transform,
+                                                   soft_hamming, abs_robust_loss, create_outgoing_mask)
+  PhotoMetrics         (the same)                  those sums accumulated over a video or a dataset without a copy or
+                                                   a synchronisation per pair: "census", "ternary", "photo"
 
 Every helper computes on the GPU through the HIP kernels of libraft_hip.so; a CPU tensor is
 copied to the current GPU and the result copied back (there is no host computation path).
@@ -402,19 +410,26 @@ def _check_metrics_devices(name, flow, flow_gt, valid):
             raise RuntimeError(f"{name}: {what} is on {t.device}, flow on {flow.device}")
 
 
+def _mask_args(mask, b, h, w):
+    """A mask [B,H,W] or [B,1,H,W] (or None) as the C entries take it: (the tensor that is read, kept alive by the
+    caller; (pointer, dtype tag, batch stride, row pitch)), strides in elements."""
+    if mask is None:
+        return None, (None, 0, 0, 0)
+    L = _lib()
+    m = mask.reshape(b, h, w) if mask.dim() == 4 else mask
+    if m.stride(2) != 1 and w > 1 or (h > 1 and m.stride(1) < w):
+        m = m.contiguous()
+    tag = L.MASK_F32 if m.dtype == torch.float32 else L.MASK_U8
+    return m, (m.data_ptr(), tag, m.stride(0), m.stride(1) if h > 1 else w)
+
+
 def _flow_metrics_call(flow, flow_gt, valid, limit, b, h, w, totals, want_map):
     """One raft_flow_metrics call on flow's device (current): (record int64 [B,16], epe_map or None)."""
     L = _lib()
     dev = flow.device
     fl, sfl = _pitched(flow, h, w)
     gt, sgt = _pitched(flow_gt, h, w)
-    vp, tag, svb, svp = None, 0, 0, 0
-    if valid is not None:
-        v = valid.reshape(b, h, w) if valid.dim() == 4 else valid
-        if v.stride(2) != 1 and w > 1 or (h > 1 and v.stride(1) < w):
-            v = v.contiguous()
-        tag = L.MASK_F32 if v.dtype == torch.float32 else L.MASK_U8
-        vp, svb, svp = v.data_ptr(), v.stride(0), (v.stride(1) if h > 1 else w)
+    v, (vp, tag, svb, svp) = _mask_args(valid, b, h, w)
     record = torch.empty(b, L.FM_SLOTS, dtype=torch.int64, device=dev)
     ws = torch.empty(L.load().raft_flow_metrics_ws_bytes(b, h, w) // 8, dtype=torch.int64, device=dev)
     emap = torch.empty(b, 1, h, w, dtype=torch.float32, device=dev) if want_map else None
@@ -512,3 +527,176 @@ class FlowMetrics:
                 "s0-10": mean(s["epe_sum_s0_10"], c["n_s0_10"]), "s10-40": mean(s["epe_sum_s10_40"], c["n_s10_40"]),
                 "s40+": mean(s["epe_sum_s40"], c["n_s40"]), "pixels": n, "images": images,
                 "nonfinite": c["n_nonfinite"]}
+
+
+PhotoErrors = collections.namedtuple(
+    "PhotoErrors", ("n_mask", "n_census", "n_valid", "n_nonfinite", "pixels", "l1_sum", "photo_sum", "hamming_sum",
+                    "census_sum", "ternary_sum", "census_map"))
+PhotoErrors.__doc__ = """Per-sample label-free scores of photo_errors: device tensors [B], the counts int64 and the
+sums float64 (include/raft_hip.h names the slots); census_map float32 [B,1,H,W] or None."""
+
+
+def _check_photo_args(name, frame1, frame2, flow, mask, patch, outgoing):
+    """The type, shape and value checks of photo_errors / PhotoMetrics.update (no device work): (b, h, w)."""
+    b, h, w = _check_flow(name, flow)
+    for what, t in (("frame1", frame1), ("frame2", frame2)):
+        if not torch.is_tensor(t):
+            raise TypeError(f"{name}: {what} must be a tensor, got {type(t).__name__}")
+        if t.dtype not in (torch.float32, torch.uint8):
+            raise TypeError(f"{name}: {what} must be float32 [B,3,H,W] or uint8 [B,H,W,3], got {t.dtype}")
+    if frame1.dtype != frame2.dtype:
+        raise TypeError(f"{name}: the frames differ in dtype: {frame1.dtype} / {frame2.dtype}")
+    want = (b, h, w, 3) if frame1.dtype == torch.uint8 else (b, 3, h, w)
+    for what, t in (("frame1", frame1), ("frame2", frame2)):
+        if tuple(t.shape) != want:
+            raise ValueError(f"{name}: {what} must be float32 [B, 3, H, W] or uint8 [B, H, W, 3] of the flow's size "
+                             f"{tuple(flow.shape)}, got {t.dtype} {tuple(t.shape)}")
+    if mask is not None:
+        if not torch.is_tensor(mask):
+            raise TypeError(f"{name}: mask must be a tensor or None, got {type(mask).__name__}")
+        if mask.dtype not in (torch.bool, torch.uint8, torch.float32):
+            raise TypeError(f"{name}: mask must be bool, uint8 or float32, got {mask.dtype}")
+        if tuple(mask.shape) not in ((b, h, w), (b, 1, h, w)):
+            raise ValueError(f"{name}: mask must be [B, H, W] or [B, 1, H, W] = {(b, h, w)}, got {tuple(mask.shape)}")
+    _check_photo_options(name, patch, outgoing)
+    return b, h, w
+
+
+def _check_photo_options(name, patch, outgoing):
+    if isinstance(patch, bool) or not isinstance(patch, int):
+        raise TypeError(f"{name}: patch must be an int, got {type(patch).__name__}")
+    if patch not in _lib().PM_PATCHES:
+        raise ValueError(f"{name}: patch must be 3, 5 or 7, got {patch}")
+    if not isinstance(outgoing, bool):
+        raise TypeError(f"{name}: outgoing must be a bool, got {type(outgoing).__name__}")
+
+
+def _check_photo_devices(name, frame1, frame2, flow, mask):
+    for what, t in (("flow", flow), ("frame1", frame1), ("frame2", frame2), ("mask", mask)):
+        if t is not None and not t.is_cuda:
+            raise RuntimeError(f"{name} runs on a ROCm GPU only: {what} is on {t.device} (no CPU path)")
+    for what, t in (("frame1", frame1), ("frame2", frame2), ("mask", mask)):
+        if t is not None and t.device != flow.device:
+            raise RuntimeError(f"{name}: {what} is on {t.device}, flow on {flow.device}")
+
+
+def _photo_metrics_call(frame1, frame2, flow, mask, patch, outgoing, b, h, w, totals, want_map):
+    """One raft_photo_metrics call on flow's device (current): (record int64 [B,16], census_map or None)."""
+    L = _lib()
+    dev = flow.device
+    fl, sfl = _pitched(flow, h, w)
+    if frame1.dtype == torch.uint8:
+        tag = L.FRAME_U8_NHWC
+        (f1, s1), (f2, s2) = (frame1.contiguous(), (0, 0, 0)), (frame2.contiguous(), (0, 0, 0))
+    else:
+        tag = L.FRAME_F32_NCHW
+        (f1, s1), (f2, s2) = _pitched(frame1, h, w), _pitched(frame2, h, w)
+    m, (mp, mtag, msb, mpitch) = _mask_args(mask, b, h, w)
+    record = torch.empty(b, L.PM_SLOTS, dtype=torch.int64, device=dev)
+    ws = torch.empty(L.load().raft_photo_metrics_ws_bytes(b, h, w, patch) // 8, dtype=torch.int64, device=dev)
+    cmap = torch.empty(b, 1, h, w, dtype=torch.float32, device=dev) if want_map else None
+    L.call("raft_photo_metrics", f1.data_ptr(), *s1, f2.data_ptr(), *s2, tag, fl.data_ptr(), *sfl, mp, mtag, msb,
+           mpitch, b, h, w, patch, L.PM_OUTGOING if outgoing else 0, record.data_ptr(),
+           None if totals is None else totals.data_ptr(), None if cmap is None else cmap.data_ptr(), ws.data_ptr(),
+           _stream())
+    return record, cmap
+
+
+def photo_errors(frame1, frame2, flow, mask=None, patch=7, outgoing=True, census_map=False):
+    """Label-free scores of a flow per sample (raft_photo_metrics: one call, two launches, no synchronisation):
+    frame 2 warped back by the flow against frame 1, photometrically and under the soft census transform.
+
+        out = stream.push(frame)   # bidirectional=True
+        utils.photo_errors(prev, frame, out.up_fw, mask=~out.occ_fw)
+
+    frame1, frame2: both float32 [B,3,H,W] in 0..255 or both uint8 [B,H,W,3]; flow: float32 [B,2,H,W] from frame
+    1 to frame 2; GPU tensors, float32 crops of larger tensors are read in place.  mask: None, or bool / uint8
+    (counted where nonzero) / float32 (where >= 0.5), [B,H,W] or [B,1,H,W]: the pixels to score, ~occlusion for
+    instance.  patch: the census patch, 3 (the reference's ternary_loss(max_distance=1)), 5 or 7 (census_loss's
+    default).  outgoing: pixels the flow pushes out of the frame do not count (create_outgoing_mask).
+    W2 = warp_frame(frame2, flow)'s float32 value bit for bit; e_c = frame1_c - W2_c; h = the soft Hamming
+    distance of the two census transforms (include/raft_hip.h has the definition).  Returns a PhotoErrors
+    namedtuple of device tensors [B]: int64 counts n_mask (scored pixels), n_census (those at least patch // 2
+    from the border), n_valid (in-frame targets, whatever the mask), n_nonfinite (scored pixels with a value that
+    is not finite: in no sum), pixels (H W); float64 sums l1_sum (|e_c|), photo_sum ((e_c^2 + 1e-6)^0.45:
+    photometric_loss), hamming_sum (h), census_sum ((h + 0.01)^0.4: census_loss's numerator), ternary_sum
+    ((h^2 + 1e-6)^0.45: ternary_loss's numerator); and census_map (float32 [B,1,H,W], h at every pixel, a
+    confidence image) if asked for, else None.  Bitwise reproducible."""
+    b, h, w = _check_photo_args("photo_errors", frame1, frame2, flow, mask, patch, outgoing)
+    _check_photo_devices("photo_errors", frame1, frame2, flow, mask)
+    L = _lib()
+    with torch.cuda.device(flow.device):
+        record, cmap = _photo_metrics_call(frame1, frame2, flow, mask, patch, outgoing, b, h, w, None,
+                                           bool(census_map))
+    sums = record.view(torch.float64)
+    nc = len(L.PM_COUNTS)
+    return PhotoErrors(*[record[:, i] for i in range(nc)], *[sums[:, nc + i] for i in range(len(L.PM_SUMS))], cmap)
+
+
+def photo_result(cnt, sums):
+    """PhotoMetrics.result()'s dict from the totals' 16 slots read as integers (cnt) and as floats (sums)."""
+    L = _lib()
+    c = dict(zip(L.PM_COUNTS, cnt))
+    s = {k: sums[len(L.PM_COUNTS) + i] for i, k in enumerate(L.PM_SUMS)}
+    nan = float("nan")
+    tainted = c["n_nonfinite"] > 0
+
+    def mean(a, n):
+        return nan if tainted or n <= 0 else a / n
+
+    images, pixels = cnt[L.PM_IMAGES], c["pixels"]
+    return {"census": nan if tainted or pixels <= 0 else s["census_sum"] / (c["n_census"] + 1e-6),
+            "ternary": mean(s["ternary_sum"], pixels), "photo": mean(s["photo_sum"], 3 * pixels),
+            "l1": mean(s["l1_sum"], 3 * c["n_mask"]), "hamming": mean(s["hamming_sum"], c["n_census"]),
+            "census_image_mean": mean(sums[L.PM_IMAGE_CENSUS_MEAN_SUM], images),
+            "valid_share": c["n_valid"] / pixels if pixels > 0 else nan, "pixels": pixels, "images": images,
+            "nonfinite": c["n_nonfinite"]}
+
+
+class PhotoMetrics:
+    """Running label-free scores over a video or a dataset, kept on the device.
+
+        m = PhotoMetrics()
+        for frame in video:
+            out = stream.push(frame)   # bidirectional=True
+            if out is not None: m.update(prev, frame, out.up_fw, mask=~out.occ_fw)
+            prev = frame
+        r = m.result()                 # r["census"], r["ternary"], r["photo"]
+
+    update() takes what photo_errors takes (shapes may change from call to call) and adds into device totals
+    without synchronising; result() synchronises once.  patch and outgoing as in photo_errors."""
+
+    def __init__(self, patch=7, outgoing=True):
+        _check_photo_options("PhotoMetrics", patch, outgoing)
+        self.patch, self.outgoing = patch, outgoing
+        self._totals = None
+
+    def update(self, frame1, frame2, flow, mask=None):
+        b, h, w = _check_photo_args("PhotoMetrics.update", frame1, frame2, flow, mask, self.patch, self.outgoing)
+        _check_photo_devices("PhotoMetrics.update", frame1, frame2, flow, mask)
+        if self._totals is not None and self._totals.device != flow.device:
+            raise RuntimeError(f"PhotoMetrics.update: the totals are on {self._totals.device}, flow on {flow.device}")
+        with torch.cuda.device(flow.device):
+            if self._totals is None:
+                self._totals = torch.zeros(_lib().PM_SLOTS, dtype=torch.int64, device=flow.device)
+            _photo_metrics_call(frame1, frame2, flow, mask, self.patch, self.outgoing, b, h, w, self._totals, False)
+        return self
+
+    def reset(self):
+        """Clear the totals (no synchronisation)."""
+        if self._totals is not None:
+            self._totals.zero_()
+
+    def result(self):
+        """The totals as a dict (one device-to-host copy).  census = census_sum / (n_census + 1e-6), the
+        reference's census_loss (0 where pairs were scored but none has an interior pixel, as there); ternary =
+        ternary_sum / pixels, ternary_loss's normalisation over all B H W; photo = photo_sum / (3 pixels),
+        photometric_loss; l1 the mean |e| per scored pixel and channel; hamming the mean h per scored interior
+        pixel; census_image_mean the mean over images (with a scored interior pixel) of census_sum / n_census;
+        valid_share = n_valid / pixels; pixels, images, nonfinite the counts.  A mean over nothing is NaN (every
+        key before the first update).  With nonfinite > 0 the means are NaN; valid_share stays a count's share."""
+        L = _lib()
+        if self._totals is None:
+            return photo_result([0] * L.PM_SLOTS, [0.0] * L.PM_SLOTS)
+        host = self._totals.cpu()
+        return photo_result(host.tolist(), host.view(torch.float64).tolist())
