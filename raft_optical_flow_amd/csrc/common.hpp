@@ -63,6 +63,9 @@ inline double env_double(const char* name, double dflt) {
   return e ? atof(e) : dflt;
 }
 
+// a [B, H, W] pixel grid the per-pixel entries take: not empty, fewer than 2^30 pixels
+inline bool size_ok(int B, int H, int W) { return B > 0 && H > 0 && W > 0 && (long)B * H * W < (1L << 30); }
+
 // work-groups of 256 threads for a grid-stride loop over n elements
 inline int grid_for(long n) {
   const long g = (n + 255) / 256;

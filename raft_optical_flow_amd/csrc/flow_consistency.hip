@@ -197,8 +197,7 @@ extern "C" int raft_fb_consistency(const float* flow_fw, long fw_batch_stride, l
                                    unsigned char* occ_fw, unsigned char* occ_bw, float* err_fw, float* err_bw,
                                    raft_stream_t stream) {
   RAFT_REQUIRE(flow_fw && flow_bw && occ_fw && occ_bw && err_fw && err_bw, "raft_fb_consistency: null pointer");
-  RAFT_REQUIRE(B > 0 && H > 0 && W > 0 && (long)B * H * W < (1L << 30), "raft_fb_consistency: bad size %d x %d x %d",
-               B, H, W);
+  RAFT_REQUIRE(size_ok(B, H, W), "raft_fb_consistency: bad size %d x %d x %d", B, H, W);
   RAFT_REQUIRE(top >= 0 && left >= 0, "raft_fb_consistency: negative crop offset");
   RAFT_REQUIRE(fw_pitch >= (long)left + W && bw_pitch >= (long)left + W && fw_batch_stride >= 0 &&
                    bw_batch_stride >= 0 && fw_chan_stride >= 0 && bw_chan_stride >= 0,

@@ -205,8 +205,6 @@ __global__ __launch_bounds__(256) void splat_convert_kernel(SplatArgs a) {
     a.density[i] = (float)a.ws[i] * 2.3283064365386963e-10f;   // one rounding (the cast); * 2^-32 is exact
 }
 
-bool warp_size_ok(int B, int H, int W) { return B > 0 && H > 0 && W > 0 && (long)B * H * W < (1L << 30); }
-
 }  // namespace
 }  // namespace raft
 
@@ -217,7 +215,7 @@ extern "C" int raft_warp_frame(const float* flow, long flow_batch_stride, long f
                                long frame_pitch, int top, int left, int B, int C, int H, int W, int flags, void* out,
                                int out_dtype, unsigned char* valid, raft_stream_t stream) {
   RAFT_REQUIRE(flow && frame && out && valid, "raft_warp_frame: null pointer");
-  RAFT_REQUIRE(warp_size_ok(B, H, W), "raft_warp_frame: bad size %d x %d x %d", B, H, W);
+  RAFT_REQUIRE(size_ok(B, H, W), "raft_warp_frame: bad size %d x %d x %d", B, H, W);
   RAFT_REQUIRE(frame_dtype == RAFT_FRAME_F32_NCHW || frame_dtype == RAFT_FRAME_U8_NHWC,
                "raft_warp_frame: unknown frame dtype tag %d", frame_dtype);
   RAFT_REQUIRE(out_dtype == RAFT_FRAME_F32_NCHW || out_dtype == RAFT_FRAME_U8_NHWC,
@@ -268,14 +266,14 @@ extern "C" int raft_warp_frame(const float* flow, long flow_batch_stride, long f
 }
 
 extern "C" size_t raft_splat_ws_bytes(int B, int H, int W) {
-  if (!warp_size_ok(B, H, W)) return 0;
+  if (!size_ok(B, H, W)) return 0;
   return (size_t)B * H * W * sizeof(unsigned long long);
 }
 
 extern "C" int raft_splat_density(const float* flow, long batch_stride, long chan_stride, long pitch, int top, int left,
                                   int B, int H, int W, void* ws, float* density, raft_stream_t stream) {
   RAFT_REQUIRE(flow && ws && density, "raft_splat_density: null pointer");
-  RAFT_REQUIRE(warp_size_ok(B, H, W), "raft_splat_density: bad size %d x %d x %d", B, H, W);
+  RAFT_REQUIRE(size_ok(B, H, W), "raft_splat_density: bad size %d x %d x %d", B, H, W);
   RAFT_REQUIRE(top >= 0 && left >= 0, "raft_splat_density: negative crop offset");
   RAFT_REQUIRE(pitch >= (long)left + W && batch_stride >= 0 && chan_stride >= 0,
                "raft_splat_density: bad strides (a row pitch holds left + W floats; strides are not negative)");

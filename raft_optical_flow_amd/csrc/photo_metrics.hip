@@ -7,7 +7,7 @@
 //                                optionally added into running totals, optionally the per-pixel soft Hamming
 //                                distance; two launches, no atomics
 //
-// The definition is in raft_hip.h.  Two kernels:
+// The definition is in raft_hip.h.
 //
 //   photo_tile_kernel<P, U8>  grid (NB, B), NB = min(tiles, RAFT_PHOTO_METRICS_MAX_BLOCKS): a function of (H, W)
 //                             only.  Work-group (p, b) takes tiles p, p + NB, ... of sample b, each 16 rows x 64
@@ -21,19 +21,16 @@
 //                             every row's P terms to the pixels whose patch holds the row: each h is summed in
 //                             row-major order of the offsets, and a row is read once for up to four pixels.  The
 //                             reads of a wave are 64 consecutive floats of one row (conflict-free for 4-byte
-//                             reads); the LDS row pitch is odd.  Then the per-pixel terms, per-thread sums in
-//                             integers and fp64, the wave's __shfl_xor butterfly, the four waves through LDS in
-//                             wave order, one partial record to ws[b][p][16].  Every slot is written on every
-//                             call.
-//   photo_finalize_kernel     one work-group adds each sample's NB partials in index order (staged through LDS,
-//                             256 at a time), writes the records, and one thread adds them into the totals in
-//                             sample order.
+//                             reads); the LDS row pitch is odd.  Then the per-pixel terms and the per-thread sums
+//                             in integers and fp64; record_common.hpp has the reduction from there
+//                             (store_partial, record_finalize_kernel) and its fixed order.
 //
 // Rounding.  Contraction is off for the whole file; `sqrtf` and `/` are correctly rounded under hipcc's
 // default -fhip-fp32-correctly-rounded-divide-sqrt; powf is the device library's (its error is measured by
 // tests/test_gpu_photo_metrics.py).  Nothing depends on the launch geometry: a pixel's values depend on the
 // inputs alone, and the order of every addition is fixed by (B, H, W, P).
 #include "common.hpp"
+#include "record_common.hpp"
 #include "warp_common.hpp"
 
 #include <cmath>
@@ -50,20 +47,24 @@ constexpr int kTileW = RAFT_PHOTO_METRICS_TILE_W;
 constexpr int kMaxBlocks = RAFT_PHOTO_METRICS_MAX_BLOCKS;
 constexpr int kMaxR = 3;                          // patch 7
 constexpr int kPitch = kTileW + 2 * kMaxR + 1;    // 71 floats: odd
-static_assert(kTileH == 16 && kTileW == 64 && kSlots == 16, "the kernels below are written for these");
+static_assert(kTileH == 16 && kTileW == 64 && kSlots == kRecordSlots, "the kernels below are written for these");
 static_assert(kPitch % 2 == 1, "the LDS row pitch is odd");
+
+// 5 counts, the last of them pixels, 5 sums; the per-image mean is CENSUS_SUM / N_CENSUS
+using Layout = RecordLayout<5, RAFT_PM_PIXELS, 5, RAFT_PM_CENSUS_SUM, RAFT_PM_N_CENSUS>;
+static_assert(Layout::kFirstSum == RAFT_PM_L1_SUM && Layout::kImages == RAFT_PM_IMAGES &&
+                  Layout::kMeanSum == RAFT_PM_IMAGE_CENSUS_MEAN_SUM && Layout::kReserved == RAFT_PM_RESERVED &&
+                  RAFT_PM_N_MASK == 0 && RAFT_PM_N_NONFINITE == Layout::kSummed - 1 &&
+                  RAFT_PM_TERNARY_SUM == RAFT_PM_IMAGES - 1,
+              "the layout is raft_hip.h's");
 
 struct PhotoArgs {
   WarpArgs w;             // frame 2 and the flow as raft_warp_frame takes them (zeros mode, C = 3); B, H, W
   const void* img1;       // float32: element (0, 0, 0, 0); uint8: the dense [B][H][W][3] base
   long i1sb, i1sc, i1pitch;
-  const void* mask;       // or null
-  long msb, mpitch;       // in elements
-  int mask_f32;
+  MaskView m;
   int outgoing;
   long long* ws;          // [B][nb][16]
-  long long* record;      // [B][16]
-  long long* totals;      // [16] or null
   float* census_map;      // [B][H][W] or null
   int nb, tiles_x, tiles;
 };
@@ -103,13 +104,6 @@ __device__ __forceinline__ void photo_pixel(const PhotoArgs& a, int b, int y, in
   valid = t.valid != 0;
 }
 
-__device__ __forceinline__ bool mask_says(const PhotoArgs& a, int b, int y, int x) {
-  if (!a.mask) return true;
-  const long off = (long)b * a.msb + (long)y * a.mpitch + x;
-  if (a.mask_f32) return static_cast<const float*>(a.mask)[off] >= 0.5f;   // a NaN fails
-  return static_cast<const unsigned char*>(a.mask)[off] != 0;
-}
-
 // one offset's term of h: d1, d2 the grey differences of the two images
 __device__ __forceinline__ float census_term(float d1, float d2) {
   const float c1 = d1 / sqrtf(0.81f + d1 * d1);
@@ -117,18 +111,6 @@ __device__ __forceinline__ float census_term(float d1, float d2) {
   const float delta = c1 - c2;
   const float q = delta * delta;
   return q / (0.1f + q);
-}
-
-__device__ __forceinline__ unsigned wave_sum(unsigned x) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d, 64);
-  return x;
-}
-
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d, 64);
-  return x;
 }
 
 template <int P, bool U8>
@@ -139,7 +121,6 @@ __global__ __launch_bounds__(256) void photo_tile_kernel(PhotoArgs a) {
   constexpr int kHalo = 2 * kTop + kTileH * 2 * R;   // ... and beside it
   __shared__ float s_g1[(kTileH + 2 * R) * kPitch];
   __shared__ float s_g2[(kTileH + 2 * R) * kPitch];
-  __shared__ long long s_part[4][kSlots];
   const int H = a.w.H, W = a.w.W;
   const int tx = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int ly0 = R + 4 * wave, lx = R + tx;         // LDS position of the thread's first pixel
@@ -221,7 +202,7 @@ __global__ __launch_bounds__(256) void photo_tile_kernel(PhotoArgs a) {
         const int y = y0 + 4 * wave + k;
         if (a.census_map) a.census_map[((long)b * H + y) * W + x] = h[k];
         acc.n_valid += valid[k];
-        if (!(mask_says(a, b, y, x) && (valid[k] || !a.outgoing))) continue;
+        if (!(mask_says(a.m, (long)b * a.m.sb + (long)y * a.m.pitch + x) && (valid[k] || !a.outgoing))) continue;
         const bool interior = x >= R && x < W - R && y >= R && y < H - R;
         ++acc.n_mask;
         acc.n_census += interior;
@@ -245,129 +226,13 @@ __global__ __launch_bounds__(256) void photo_tile_kernel(PhotoArgs a) {
       __syncthreads();   // every read of this tile's LDS is done before the next tile is written
     }
 
-    const unsigned cnts[4] = {wave_sum(acc.n_mask), wave_sum(acc.n_census), wave_sum(acc.n_valid),
-                              wave_sum(acc.n_nonfinite)};
-    const double sums[5] = {wave_sum(acc.l1), wave_sum(acc.photo), wave_sum(acc.hamming), wave_sum(acc.census),
-                            wave_sum(acc.ternary)};
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) s_part[wave][RAFT_PM_N_MASK + k] = (long long)cnts[k];
-#pragma unroll
-      for (int k = 0; k < 5; ++k) s_part[wave][RAFT_PM_L1_SUM + k] = __double_as_longlong(sums[k]);
-    }
-    __syncthreads();
-    if (threadIdx.x < kSlots) {
-      const int s = threadIdx.x;
-      long long out = 0;   // pixels (the finalize kernel writes it), the totals' slots and the reserved ones
-      if (s < RAFT_PM_PIXELS) {
-        out = s_part[0][s] + s_part[1][s] + s_part[2][s] + s_part[3][s];
-      } else if (s >= RAFT_PM_L1_SUM && s < RAFT_PM_IMAGES) {
-        const double d = ((__longlong_as_double(s_part[0][s]) + __longlong_as_double(s_part[1][s])) +
-                          __longlong_as_double(s_part[2][s])) +
-                         __longlong_as_double(s_part[3][s]);
-        out = __double_as_longlong(d);
-      }
-      a.ws[((long)b * a.nb + blockIdx.x) * kSlots + s] = out;
-    }
-    __syncthreads();
+    const unsigned cnts[Layout::kSummed] = {acc.n_mask, acc.n_census, acc.n_valid, acc.n_nonfinite};
+    const double sums[Layout::kSums] = {acc.l1, acc.photo, acc.hamming, acc.census, acc.ternary};
+    store_partial<Layout>(cnts, sums, a.ws + ((long)b * a.nb + blockIdx.x) * kSlots, wave);
   }
 }
 
-// One work-group.  The partials are staged in LDS, 256 of them at a time, by all 256 threads, so that the adds
-// in index order do not wait on one global load each.  Where a sample has fewer than 256 partials several
-// samples (whole ones, 16 at most) are staged together and thread (sample, slot) adds its sample's; a sample
-// with more is staged alone in runs of 256 and its 16 threads carry their sums from run to run.  Thread 0
-// carries the totals in registers and adds each sample's record in sample order.
-constexpr int kStage = 256;   // partials per staging pass: 256 x 16 x 8 B = 32 KiB
-
-__global__ __launch_bounds__(256) void photo_finalize_kernel(PhotoArgs a) {
-  __shared__ long long s_ws[kStage * kSlots];
-  __shared__ long long s_rec[256];   // the staged samples' records: (sample, slot) = thread
-  const int tid = threadIdx.x;
-  const int nb = a.nb;
-  const int per = nb >= kStage ? 1 : (kStage / nb < 256 / kSlots ? kStage / nb : 256 / kSlots);
-  const long long pixels = (long long)a.w.H * a.w.W;
-  const bool totals = a.totals != nullptr && tid == 0;
-  long long cnt[RAFT_PM_L1_SUM] = {};
-  double sum[5] = {};
-  double mean_sum = 0.0;
-  long long images = 0;
-  if (totals) {
-#pragma unroll
-    for (int s = 0; s < RAFT_PM_L1_SUM; ++s) cnt[s] = a.totals[s];
-#pragma unroll
-    for (int k = 0; k < 5; ++k) sum[k] = __longlong_as_double(a.totals[RAFT_PM_L1_SUM + k]);
-    images = a.totals[RAFT_PM_IMAGES];
-    mean_sum = __longlong_as_double(a.totals[RAFT_PM_IMAGE_CENSUS_MEAN_SUM]);
-  }
-  for (int b0 = 0; b0 < a.w.B; b0 += per) {
-    const int nsamp = a.w.B - b0 < per ? a.w.B - b0 : per;
-    const int j = tid / kSlots, s = tid - j * kSlots;    // the thread's (sample, slot), where tid < nsamp * 16
-    long long icnt = 0;
-    double dsum = 0.0;
-    for (int p0 = 0; p0 < nb; p0 += kStage) {            // (one pass unless per == 1)
-      const int pn = nb - p0 < kStage ? nb - p0 : kStage;
-      const int staged = nsamp * pn * kSlots;            // <= kStage * 16 (nsamp > 1 only where pn == nb)
-      const long long* src = a.ws + ((long)b0 * nb + p0) * kSlots;
-      {
-        long long v[kStage * kSlots / 256];
-#pragma unroll
-        for (int k = 0; k < kStage * kSlots / 256; ++k) v[k] = tid + 256 * k < staged ? src[tid + 256 * k] : 0;
-#pragma unroll
-        for (int k = 0; k < kStage * kSlots / 256; ++k)
-          if (tid + 256 * k < staged) s_ws[tid + 256 * k] = v[k];
-      }
-      __syncthreads();
-      if (tid < nsamp * kSlots) {
-        const long long* part = s_ws + j * pn * kSlots + s;
-        if (s < RAFT_PM_PIXELS) {
-#pragma unroll 16
-          for (int p = 0; p < pn; ++p) icnt += part[p * kSlots];
-        } else if (s >= RAFT_PM_L1_SUM && s < RAFT_PM_IMAGES) {
-#pragma unroll 16   // (the reads are issued ahead of the chain of adds; the order of the adds stays)
-          for (int p = 0; p < pn; ++p) dsum += __longlong_as_double(part[p * kSlots]);
-        }
-      }
-      __syncthreads();   // s_ws is read before the next pass overwrites it
-    }
-    if (tid < nsamp * kSlots) {
-      long long out = 0;   // the totals' slots and the reserved ones: 0 in a sample's record
-      if (s < RAFT_PM_PIXELS) out = icnt;
-      else if (s == RAFT_PM_PIXELS) out = pixels;
-      else if (s < RAFT_PM_IMAGES) out = __double_as_longlong(dsum);
-      a.record[(long)b0 * kSlots + tid] = out;
-      s_rec[tid] = out;
-    }
-    __syncthreads();
-    if (totals) {
-      for (int q = 0; q < nsamp; ++q) {
-        const long long* r = s_rec + q * kSlots;
-#pragma unroll
-        for (int k = 0; k < RAFT_PM_L1_SUM; ++k) cnt[k] += r[k];
-#pragma unroll
-        for (int k = 0; k < 5; ++k) sum[k] += __longlong_as_double(r[RAFT_PM_L1_SUM + k]);
-        if (r[RAFT_PM_N_CENSUS] > 0) {
-          ++images;
-          mean_sum += __longlong_as_double(r[RAFT_PM_CENSUS_SUM]) / (double)r[RAFT_PM_N_CENSUS];
-        }
-      }
-    }
-    __syncthreads();   // thread 0 has read s_rec before the next pass overwrites it
-  }
-  if (!totals) return;
-#pragma unroll
-  for (int k = 0; k < RAFT_PM_L1_SUM; ++k) a.totals[k] = cnt[k];
-#pragma unroll
-  for (int k = 0; k < 5; ++k) a.totals[RAFT_PM_L1_SUM + k] = __double_as_longlong(sum[k]);
-  a.totals[RAFT_PM_IMAGES] = images;
-  a.totals[RAFT_PM_IMAGE_CENSUS_MEAN_SUM] = __double_as_longlong(mean_sum);
-#pragma unroll
-  for (int k = RAFT_PM_RESERVED; k < kSlots; ++k) a.totals[k] = 0;
-}
-
-bool photo_size_ok(int B, int H, int W, int patch) {
-  return B > 0 && H > 0 && W > 0 && (long)B * H * W < (1L << 30) && (patch == 3 || patch == 5 || patch == 7);
-}
+bool patch_ok(int patch) { return patch == 3 || patch == 5 || patch == 7; }
 
 long photo_tiles_x(int W) { return ((long)W + kTileW - 1) / kTileW; }
 long photo_tiles(int H, int W) { return (((long)H + kTileH - 1) / kTileH) * photo_tiles_x(W); }
@@ -392,7 +257,7 @@ void launch_tiles(const PhotoArgs& a, bool u8, dim3 grid, hipStream_t s) {
 using namespace raft;
 
 extern "C" size_t raft_photo_metrics_ws_bytes(int B, int H, int W, int patch) {
-  if (!photo_size_ok(B, H, W, patch)) return 0;
+  if (!(size_ok(B, H, W) && patch_ok(patch))) return 0;
   return (size_t)B * photo_blocks(H, W) * kSlots * sizeof(long long);
 }
 
@@ -403,12 +268,12 @@ extern "C" int raft_photo_metrics(const void* frame1, long f1_batch_stride, long
                                   long mask_pitch, int B, int H, int W, int patch, int flags, void* record,
                                   void* totals, float* census_map, void* ws, raft_stream_t stream) {
   RAFT_REQUIRE(frame1 && frame2 && flow && record && ws, "raft_photo_metrics: null pointer");
-  RAFT_REQUIRE(patch == 3 || patch == 5 || patch == 7, "raft_photo_metrics: patch must be 3, 5 or 7, got %d", patch);
-  RAFT_REQUIRE(photo_size_ok(B, H, W, patch), "raft_photo_metrics: bad size %d x %d x %d", B, H, W);
+  const char* who = "raft_photo_metrics";
+  RAFT_REQUIRE(patch_ok(patch), "raft_photo_metrics: patch must be 3, 5 or 7, got %d", patch);
+  if (const int rc = check_size(who, B, H, W)) return rc;
   RAFT_REQUIRE(frame_dtype == RAFT_FRAME_F32_NCHW || frame_dtype == RAFT_FRAME_U8_NHWC,
                "raft_photo_metrics: unknown frame dtype tag %d", frame_dtype);
-  RAFT_REQUIRE(!mask || mask_dtype == RAFT_MASK_U8 || mask_dtype == RAFT_MASK_F32,
-               "raft_photo_metrics: unknown mask dtype tag %d", mask_dtype);
+  if (const int rc = check_mask(who, mask, mask_dtype, mask_batch_stride, mask_pitch, W)) return rc;
   RAFT_REQUIRE((flags & ~RAFT_PHOTO_OUTGOING) == 0, "raft_photo_metrics: unknown flags %d", flags);
   const bool u8 = frame_dtype == RAFT_FRAME_U8_NHWC;
   RAFT_REQUIRE(flow_pitch >= W && flow_batch_stride >= 0 && flow_chan_stride >= 0,
@@ -416,24 +281,11 @@ extern "C" int raft_photo_metrics(const void* frame1, long f1_batch_stride, long
   RAFT_REQUIRE(u8 || (f1_pitch >= W && f1_batch_stride >= 0 && f1_chan_stride >= 0 && f2_pitch >= W &&
                       f2_batch_stride >= 0 && f2_chan_stride >= 0),
                "raft_photo_metrics: bad frame strides (a row pitch holds W floats; strides are not negative)");
-  RAFT_REQUIRE(!mask || (mask_pitch >= W && mask_batch_stride >= 0),
-               "raft_photo_metrics: bad mask strides (a row pitch holds W elements; strides are not negative)");
-  const bool mask_f32 = mask && mask_dtype == RAFT_MASK_F32;
   RAFT_REQUIRE((((uintptr_t)flow | (uintptr_t)census_map) & 3) == 0 &&
-                   (u8 || (((uintptr_t)frame1 | (uintptr_t)frame2) & 3) == 0) &&
-                   (!mask_f32 || ((uintptr_t)mask & 3) == 0) &&
-                   (((uintptr_t)record | (uintptr_t)totals | (uintptr_t)ws) & 7) == 0,
-               "raft_photo_metrics: misaligned pointer (float32 frames, flow, float32 mask, census_map 4 bytes; "
-               "record, totals, ws 8)");
+                   (u8 || (((uintptr_t)frame1 | (uintptr_t)frame2) & 3) == 0),
+               "raft_photo_metrics: misaligned pointer (float32 frames, flow, census_map 4 bytes)");
   const void* ins[4] = {frame1, frame2, flow, mask};
-  const void* outs[4] = {record, ws, totals, census_map};
-  for (int i = 0; i < 4; ++i) {
-    if (!outs[i]) continue;
-    for (int j = 0; j < 4; ++j)
-      RAFT_REQUIRE(outs[i] != ins[j], "raft_photo_metrics: an output aliases an input or another output");
-    for (int j = 0; j < i; ++j)
-      RAFT_REQUIRE(outs[i] != outs[j], "raft_photo_metrics: an output aliases an input or another output");
-  }
+  if (const int rc = check_outputs(who, record, totals, ws, census_map, ins, 4)) return rc;
   PhotoArgs a;
   a.w.flow = flow;
   a.w.fsb = flow_batch_stride;
@@ -454,14 +306,9 @@ extern "C" int raft_photo_metrics(const void* frame1, long f1_batch_stride, long
   a.i1sb = f1_batch_stride;
   a.i1sc = f1_chan_stride;
   a.i1pitch = f1_pitch;
-  a.mask = mask;
-  a.msb = mask ? mask_batch_stride : 0;
-  a.mpitch = mask ? mask_pitch : 0;
-  a.mask_f32 = mask_f32 ? 1 : 0;
+  a.m = mask_view(mask, mask_dtype, mask_batch_stride, mask_pitch);
   a.outgoing = (flags & RAFT_PHOTO_OUTGOING) ? 1 : 0;
   a.ws = static_cast<long long*>(ws);
-  a.record = static_cast<long long*>(record);
-  a.totals = static_cast<long long*>(totals);
   a.census_map = census_map;
   a.nb = photo_blocks(H, W);
   a.tiles_x = (int)photo_tiles_x(W);
@@ -476,6 +323,5 @@ extern "C" int raft_photo_metrics(const void* frame1, long f1_batch_stride, long
     launch_tiles<7>(a, u8, grid, s);
   const int rc = check_launch("raft_photo_metrics (tiles)");
   if (rc) return rc;
-  hipLaunchKernelGGL(photo_finalize_kernel, dim3(1), dim3(256), 0, s, a);
-  return check_launch("raft_photo_metrics");
+  return launch_finalize<Layout>(who, ws, record, totals, B, a.nb, H, W, s);
 }

@@ -200,34 +200,14 @@ def fb_consistency(flow_fw, flow_bw, alpha=0.01, beta=0.5):
     g = bilinear G(p), err = |F(x) + g|^2, occ = err > alpha (|F(x)|^2 + |g|^2) + beta (the UnFlow criterion
     with its published defaults; include/raft_hip.h has the full definition).  Direction bw swaps F and G.
     Returns (occ_fw, occ_bw, err_fw, err_bw): bool and float32 [B,1,H,W]."""
-    for name, t in (("flow_fw", flow_fw), ("flow_bw", flow_bw)):
-        if not torch.is_tensor(t):
-            raise TypeError(f"fb_consistency: {name} must be a tensor, got {type(t).__name__}")
-        if t.dtype != torch.float32:
-            raise TypeError(f"fb_consistency: {name} must be float32, got {t.dtype}")
-        if t.dim() != 4 or t.shape[1] != 2 or t.numel() == 0:
-            raise ValueError(f"fb_consistency: {name} must be [B, 2, H, W], got {tuple(t.shape)}")
+    for what, t in (("flow_fw", flow_fw), ("flow_bw", flow_bw)):
+        b, h, w = _check_flow("fb_consistency", t, what)
     if flow_fw.shape != flow_bw.shape:
         raise ValueError(f"fb_consistency: the flows differ in shape: {tuple(flow_fw.shape)} / {tuple(flow_bw.shape)}")
     alpha, beta = check_fb_params(alpha, beta)
-    for name, t in (("flow_fw", flow_fw), ("flow_bw", flow_bw)):
-        if not t.is_cuda:
-            raise RuntimeError(f"fb_consistency runs on a ROCm GPU only: {name} is on {t.device} (no CPU path)")
-    if flow_fw.device != flow_bw.device:
-        raise RuntimeError(f"fb_consistency: the flows are on {flow_fw.device} and {flow_bw.device}")
-    b, _, h, w = flow_fw.shape
-    if b * h * w >= 1 << 30:
-        raise ValueError(f"fb_consistency: {b} x {h} x {w} pixels exceed 2^30")
-
-    def view(t):
-        # unit element stride and a row pitch that holds a row; anything else (a transposed or expanded
-        # view) is copied once
-        if t.stride(3) != 1 and w > 1 or (h > 1 and t.stride(2) < w):
-            t = t.contiguous()
-        return t, (t.stride(0), t.stride(1), t.stride(2) if h > 1 else w)
-
+    _check_devices("fb_consistency", "flow_fw", flow_fw=flow_fw, flow_bw=flow_bw)
     with torch.cuda.device(flow_fw.device):
-        (fw, sfw), (bw, sbw) = view(flow_fw), view(flow_bw)
+        (fw, sfw), (bw, sbw) = _pitched(flow_fw, h, w), _pitched(flow_bw, h, w)
         occ = [torch.empty(b, 1, h, w, dtype=torch.uint8, device=fw.device) for _ in range(2)]
         err = [torch.empty(b, 1, h, w, device=fw.device) for _ in range(2)]
         _lib().call("raft_fb_consistency", fw.data_ptr(), *sfw, bw.data_ptr(), *sbw, 0, 0, b, h, w, alpha, beta,
@@ -255,18 +235,42 @@ def ingest_frame(frame, mode="sintel"):
     return rows, padded, pad
 
 
-def _check_flow(name, flow):
-    """(B, H, W) of a flow, float32 [B,2,H,W] with fewer than 2^30 pixels; raises otherwise."""
+def _check_flow(name, flow, what="flow"):
+    """(B, H, W) of a flow (the argument `what`), float32 [B,2,H,W] with fewer than 2^30 pixels; raises otherwise."""
     if not torch.is_tensor(flow):
-        raise TypeError(f"{name}: flow must be a tensor, got {type(flow).__name__}")
+        raise TypeError(f"{name}: {what} must be a tensor, got {type(flow).__name__}")
     if flow.dtype != torch.float32:
-        raise TypeError(f"{name}: flow must be float32, got {flow.dtype}")
+        raise TypeError(f"{name}: {what} must be float32, got {flow.dtype}")
     if flow.dim() != 4 or flow.shape[1] != 2 or flow.numel() == 0:
-        raise ValueError(f"{name}: flow must be [B, 2, H, W], got {tuple(flow.shape)}")
+        raise ValueError(f"{name}: {what} must be [B, 2, H, W], got {tuple(flow.shape)}")
     b, _, h, w = flow.shape
     if b * h * w >= 1 << 30:
         raise ValueError(f"{name}: {b} x {h} x {w} pixels exceed 2^30")
     return b, h, w
+
+
+def _check_devices(name, anchor="flow", **tensors):
+    """Every named tensor (None: absent) is on a GPU, and on the anchor's (one of them)."""
+    tensors = {what: t for what, t in tensors.items() if t is not None}
+    for what, t in tensors.items():
+        if not t.is_cuda:
+            raise RuntimeError(f"{name} runs on a ROCm GPU only: {what} is on {t.device} (no CPU path)")
+    dev = tensors[anchor].device
+    for what, t in tensors.items():
+        if t.device != dev:
+            raise RuntimeError(f"{name}: {what} is on {t.device}, {anchor} on {dev}")
+
+
+def _check_mask(name, what, mask, b, h, w):
+    """A scorer's mask argument `what`: None, or bool / uint8 / float32 [B,H,W] or [B,1,H,W]; raises otherwise."""
+    if mask is None:
+        return
+    if not torch.is_tensor(mask):
+        raise TypeError(f"{name}: {what} must be a tensor or None, got {type(mask).__name__}")
+    if mask.dtype not in (torch.bool, torch.uint8, torch.float32):
+        raise TypeError(f"{name}: {what} must be bool, uint8 or float32, got {mask.dtype}")
+    if tuple(mask.shape) not in ((b, h, w), (b, 1, h, w)):
+        raise ValueError(f"{name}: {what} must be [B, H, W] or [B, 1, H, W] = {(b, h, w)}, got {tuple(mask.shape)}")
 
 
 def _pitched(t, h, w):
@@ -323,11 +327,7 @@ def warp_frame(frame, flow, padding="zeros", out_dtype=None):
         raise ValueError(f"warp_frame: frame {tuple(frame.shape)} and flow {tuple(flow.shape)} differ in size")
     if out_u8 and c != 3:
         raise ValueError(f"warp_frame: a uint8 result needs 3 channels, the frame has {c}")
-    for name, t in (("frame", frame), ("flow", flow)):
-        if not t.is_cuda:
-            raise RuntimeError(f"warp_frame runs on a ROCm GPU only: {name} is on {t.device} (no CPU path)")
-    if frame.device != flow.device:
-        raise RuntimeError(f"warp_frame: frame is on {frame.device}, flow on {flow.device}")
+    _check_devices("warp_frame", frame=frame, flow=flow)
     with torch.cuda.device(flow.device):
         fl, sfl = _pitched(flow, h, w)
         if in_u8:
@@ -353,8 +353,7 @@ def splat_density(flow):
     flow [B,2,H,W] float32 on a GPU, any strides."""
     L = _lib()
     b, h, w = _check_flow("splat_density", flow)
-    if not flow.is_cuda:
-        raise RuntimeError(f"splat_density runs on a ROCm GPU only: flow is on {flow.device} (no CPU path)")
+    _check_devices("splat_density", flow=flow)
     with torch.cuda.device(flow.device):
         fl, sfl = _pitched(flow, h, w)
         ws = torch.empty(L.load().raft_splat_ws_bytes(b, h, w) // 8, dtype=torch.int64, device=fl.device)
@@ -371,7 +370,7 @@ float64 (include/raft_hip.h names the slots); epe_map float32 [B,1,H,W] or None.
 
 
 def _check_metrics_args(name, flow, flow_gt, valid, gt_limit):
-    """The type, shape and value checks of flow_errors / FlowMetrics.update (no device work): returns
+    """The type, shape, value and device checks of flow_errors / FlowMetrics.update (no device work): returns
     (b, h, w, gt_limit as a float, 0.0 for none)."""
     b, h, w = _check_flow(name, flow)
     if not torch.is_tensor(flow_gt):
@@ -380,15 +379,10 @@ def _check_metrics_args(name, flow, flow_gt, valid, gt_limit):
         raise TypeError(f"{name}: flow_gt must be float32, got {flow_gt.dtype}")
     if tuple(flow_gt.shape) != tuple(flow.shape):
         raise ValueError(f"{name}: flow_gt {tuple(flow_gt.shape)} and flow {tuple(flow.shape)} differ in shape")
-    if valid is not None:
-        if not torch.is_tensor(valid):
-            raise TypeError(f"{name}: valid must be a tensor or None, got {type(valid).__name__}")
-        if valid.dtype not in (torch.bool, torch.uint8, torch.float32):
-            raise TypeError(f"{name}: valid must be bool, uint8 or float32, got {valid.dtype}")
-        if tuple(valid.shape) not in ((b, h, w), (b, 1, h, w)):
-            raise ValueError(f"{name}: valid must be [B, H, W] or [B, 1, H, W] = {(b, h, w)}, got "
-                             f"{tuple(valid.shape)}")
-    return b, h, w, _check_gt_limit(name, gt_limit)
+    _check_mask(name, "valid", valid, b, h, w)
+    limit = _check_gt_limit(name, gt_limit)
+    _check_devices(name, flow=flow, flow_gt=flow_gt, valid=valid)
+    return b, h, w, limit
 
 
 def _check_gt_limit(name, gt_limit):
@@ -399,15 +393,6 @@ def _check_gt_limit(name, gt_limit):
     if not (0.0 < float(gt_limit) < float("inf")):
         raise ValueError(f"{name}: gt_limit must be positive and finite (None: no limit), got {gt_limit!r}")
     return float(gt_limit)
-
-
-def _check_metrics_devices(name, flow, flow_gt, valid):
-    for what, t in (("flow", flow), ("flow_gt", flow_gt), ("valid", valid)):
-        if t is not None and not t.is_cuda:
-            raise RuntimeError(f"{name} runs on a ROCm GPU only: {what} is on {t.device} (no CPU path)")
-    for what, t in (("flow_gt", flow_gt), ("valid", valid)):
-        if t is not None and t.device != flow.device:
-            raise RuntimeError(f"{name}: {what} is on {t.device}, flow on {flow.device}")
 
 
 def _mask_args(mask, b, h, w):
@@ -423,20 +408,64 @@ def _mask_args(mask, b, h, w):
     return m, (m.data_ptr(), tag, m.stride(0), m.stride(1) if h > 1 else w)
 
 
+def _record_call(entry, head, size, dev, totals, want_map):
+    """One call of a scorer's C entry on device dev (current): head are its arguments up to record, size the
+    arguments of its _ws_bytes, (b, h, w) first.  Returns (record int64 [B,16], the per-pixel map or None)."""
+    L = _lib()
+    b, h, w = size[:3]
+    record = torch.empty(b, L.FM_SLOTS, dtype=torch.int64, device=dev)
+    ws = torch.empty(getattr(L.load(), entry + "_ws_bytes")(*size) // 8, dtype=torch.int64, device=dev)
+    pmap = torch.empty(b, 1, h, w, dtype=torch.float32, device=dev) if want_map else None
+    L.call(entry, *head, record.data_ptr(), None if totals is None else totals.data_ptr(),
+           None if pmap is None else pmap.data_ptr(), ws.data_ptr(), _stream())
+    return record, pmap
+
+
+def _record_tuple(cls, counts, sums, record, pmap):
+    """A scorer's record [B,16] as its namedtuple of [B] views: the counts, the sums as float64, the map."""
+    f64, nc = record.view(torch.float64), len(counts)
+    return cls(*[record[:, i] for i in range(nc)], *[f64[:, nc + i] for i in range(len(sums))], pmap)
+
+
+def _named_slots(counts, sums, cnt, val):
+    """The 16 slots read as integers (cnt) and as floats (val) -> ({count name: int}, {sum name: float})."""
+    return dict(zip(counts, cnt)), {k: val[len(counts) + i] for i, k in enumerate(sums)}
+
+
+class _RunningTotals:
+    """The [16] int64 device totals a scorer's entry adds into (FlowMetrics, PhotoMetrics)."""
+
+    _totals = None
+
+    def _totals_on(self, name, flow):
+        """The totals, on flow's device: allocated at the first update."""
+        if self._totals is None:
+            self._totals = torch.zeros(_lib().FM_SLOTS, dtype=torch.int64, device=flow.device)
+        elif self._totals.device != flow.device:
+            raise RuntimeError(f"{name}: the totals are on {self._totals.device}, flow on {flow.device}")
+        return self._totals
+
+    def reset(self):
+        """Clear the totals (no synchronisation)."""
+        if self._totals is not None:
+            self._totals.zero_()
+
+    def _host(self):
+        """The 16 slots as integers and as floats (one device-to-host copy; zeros before the first update)."""
+        if self._totals is None:
+            n = _lib().FM_SLOTS
+            return [0] * n, [0.0] * n
+        host = self._totals.cpu()
+        return host.tolist(), host.view(torch.float64).tolist()
+
+
 def _flow_metrics_call(flow, flow_gt, valid, limit, b, h, w, totals, want_map):
     """One raft_flow_metrics call on flow's device (current): (record int64 [B,16], epe_map or None)."""
-    L = _lib()
-    dev = flow.device
     fl, sfl = _pitched(flow, h, w)
     gt, sgt = _pitched(flow_gt, h, w)
-    v, (vp, tag, svb, svp) = _mask_args(valid, b, h, w)
-    record = torch.empty(b, L.FM_SLOTS, dtype=torch.int64, device=dev)
-    ws = torch.empty(L.load().raft_flow_metrics_ws_bytes(b, h, w) // 8, dtype=torch.int64, device=dev)
-    emap = torch.empty(b, 1, h, w, dtype=torch.float32, device=dev) if want_map else None
-    L.call("raft_flow_metrics", fl.data_ptr(), *sfl, gt.data_ptr(), *sgt, vp, tag, svb, svp, b, h, w, limit,
-           record.data_ptr(), None if totals is None else totals.data_ptr(),
-           None if emap is None else emap.data_ptr(), ws.data_ptr(), _stream())
-    return record, emap
+    v, vargs = _mask_args(valid, b, h, w)
+    head = (fl.data_ptr(), *sfl, gt.data_ptr(), *sgt, *vargs, b, h, w, limit)
+    return _record_call("raft_flow_metrics", head, (b, h, w), flow.device, totals, want_map)
 
 
 def flow_errors(flow, flow_gt, valid=None, gt_limit=None, epe_map=False):
@@ -453,16 +482,13 @@ def flow_errors(flow, flow_gt, valid=None, gt_limit=None, epe_map=False):
     mag), float64 sums epe_sum and epe_sum_s0_10 / _s10_40 / _s40, and epe_map (float32 [B,1,H,W], NaN at invalid
     pixels) if asked for, else None.  Bitwise reproducible; include/raft_hip.h has the definition."""
     b, h, w, limit = _check_metrics_args("flow_errors", flow, flow_gt, valid, gt_limit)
-    _check_metrics_devices("flow_errors", flow, flow_gt, valid)
     L = _lib()
     with torch.cuda.device(flow.device):
         record, emap = _flow_metrics_call(flow, flow_gt, valid, limit, b, h, w, None, bool(epe_map))
-    sums = record.view(torch.float64)
-    nc = len(L.FM_COUNTS)
-    return FlowErrors(*[record[:, i] for i in range(nc)], *[sums[:, nc + i] for i in range(len(L.FM_SUMS))], emap)
+    return _record_tuple(FlowErrors, L.FM_COUNTS, L.FM_SUMS, record, emap)
 
 
-class FlowMetrics:
+class FlowMetrics(_RunningTotals):
     """Running error statistics over a dataset, kept on the device: evaluate.py's validate_* loops without the
     per-pair `.cpu()` copy and synchronisation.
 
@@ -479,23 +505,13 @@ class FlowMetrics:
 
     def __init__(self, gt_limit=None):
         self.gt_limit = _check_gt_limit("FlowMetrics", gt_limit)
-        self._totals = None
 
     def update(self, flow, flow_gt, valid=None):
         b, h, w, _ = _check_metrics_args("FlowMetrics.update", flow, flow_gt, valid, None)
-        _check_metrics_devices("FlowMetrics.update", flow, flow_gt, valid)
-        if self._totals is not None and self._totals.device != flow.device:
-            raise RuntimeError(f"FlowMetrics.update: the totals are on {self._totals.device}, flow on {flow.device}")
+        totals = self._totals_on("FlowMetrics.update", flow)
         with torch.cuda.device(flow.device):
-            if self._totals is None:
-                self._totals = torch.zeros(_lib().FM_SLOTS, dtype=torch.int64, device=flow.device)
-            _flow_metrics_call(flow, flow_gt, valid, self.gt_limit, b, h, w, self._totals, False)
+            _flow_metrics_call(flow, flow_gt, valid, self.gt_limit, b, h, w, totals, False)
         return self
-
-    def reset(self):
-        """Clear the totals (no synchronisation)."""
-        if self._totals is not None:
-            self._totals.zero_()
 
     def result(self):
         """The totals as a dict (one device-to-host copy).  epe = epe_sum / n over all valid pixels; "1px", "3px",
@@ -504,13 +520,8 @@ class FlowMetrics:
         nonfinite the counts.  A mean over nothing is NaN.  With nonfinite > 0 the means and f1 are NaN (a
         non-finite prediction taints the reference's means in the same way); the shares stay counts over n."""
         L = _lib()
-        if self._totals is None:
-            cnt, sums = [0] * L.FM_SLOTS, [0.0] * L.FM_SLOTS
-        else:
-            host = self._totals.cpu()
-            cnt, sums = host.tolist(), host.view(torch.float64).tolist()
-        c = dict(zip(L.FM_COUNTS, cnt))
-        s = {k: sums[len(L.FM_COUNTS) + i] for i, k in enumerate(L.FM_SUMS)}
+        cnt, sums = self._host()
+        c, s = _named_slots(L.FM_COUNTS, L.FM_SUMS, cnt, sums)
         nan = float("nan")
         tainted = c["n_nonfinite"] > 0
 
@@ -537,7 +548,7 @@ sums float64 (include/raft_hip.h names the slots); census_map float32 [B,1,H,W] 
 
 
 def _check_photo_args(name, frame1, frame2, flow, mask, patch, outgoing):
-    """The type, shape and value checks of photo_errors / PhotoMetrics.update (no device work): (b, h, w)."""
+    """The type, shape, value and device checks of photo_errors / PhotoMetrics.update (no device work): (b, h, w)."""
     b, h, w = _check_flow(name, flow)
     for what, t in (("frame1", frame1), ("frame2", frame2)):
         if not torch.is_tensor(t):
@@ -551,14 +562,9 @@ def _check_photo_args(name, frame1, frame2, flow, mask, patch, outgoing):
         if tuple(t.shape) != want:
             raise ValueError(f"{name}: {what} must be float32 [B, 3, H, W] or uint8 [B, H, W, 3] of the flow's size "
                              f"{tuple(flow.shape)}, got {t.dtype} {tuple(t.shape)}")
-    if mask is not None:
-        if not torch.is_tensor(mask):
-            raise TypeError(f"{name}: mask must be a tensor or None, got {type(mask).__name__}")
-        if mask.dtype not in (torch.bool, torch.uint8, torch.float32):
-            raise TypeError(f"{name}: mask must be bool, uint8 or float32, got {mask.dtype}")
-        if tuple(mask.shape) not in ((b, h, w), (b, 1, h, w)):
-            raise ValueError(f"{name}: mask must be [B, H, W] or [B, 1, H, W] = {(b, h, w)}, got {tuple(mask.shape)}")
+    _check_mask(name, "mask", mask, b, h, w)
     _check_photo_options(name, patch, outgoing)
+    _check_devices(name, flow=flow, frame1=frame1, frame2=frame2, mask=mask)
     return b, h, w
 
 
@@ -571,19 +577,9 @@ def _check_photo_options(name, patch, outgoing):
         raise TypeError(f"{name}: outgoing must be a bool, got {type(outgoing).__name__}")
 
 
-def _check_photo_devices(name, frame1, frame2, flow, mask):
-    for what, t in (("flow", flow), ("frame1", frame1), ("frame2", frame2), ("mask", mask)):
-        if t is not None and not t.is_cuda:
-            raise RuntimeError(f"{name} runs on a ROCm GPU only: {what} is on {t.device} (no CPU path)")
-    for what, t in (("frame1", frame1), ("frame2", frame2), ("mask", mask)):
-        if t is not None and t.device != flow.device:
-            raise RuntimeError(f"{name}: {what} is on {t.device}, flow on {flow.device}")
-
-
 def _photo_metrics_call(frame1, frame2, flow, mask, patch, outgoing, b, h, w, totals, want_map):
     """One raft_photo_metrics call on flow's device (current): (record int64 [B,16], census_map or None)."""
     L = _lib()
-    dev = flow.device
     fl, sfl = _pitched(flow, h, w)
     if frame1.dtype == torch.uint8:
         tag = L.FRAME_U8_NHWC
@@ -591,15 +587,10 @@ def _photo_metrics_call(frame1, frame2, flow, mask, patch, outgoing, b, h, w, to
     else:
         tag = L.FRAME_F32_NCHW
         (f1, s1), (f2, s2) = _pitched(frame1, h, w), _pitched(frame2, h, w)
-    m, (mp, mtag, msb, mpitch) = _mask_args(mask, b, h, w)
-    record = torch.empty(b, L.PM_SLOTS, dtype=torch.int64, device=dev)
-    ws = torch.empty(L.load().raft_photo_metrics_ws_bytes(b, h, w, patch) // 8, dtype=torch.int64, device=dev)
-    cmap = torch.empty(b, 1, h, w, dtype=torch.float32, device=dev) if want_map else None
-    L.call("raft_photo_metrics", f1.data_ptr(), *s1, f2.data_ptr(), *s2, tag, fl.data_ptr(), *sfl, mp, mtag, msb,
-           mpitch, b, h, w, patch, L.PM_OUTGOING if outgoing else 0, record.data_ptr(),
-           None if totals is None else totals.data_ptr(), None if cmap is None else cmap.data_ptr(), ws.data_ptr(),
-           _stream())
-    return record, cmap
+    m, margs = _mask_args(mask, b, h, w)
+    head = (f1.data_ptr(), *s1, f2.data_ptr(), *s2, tag, fl.data_ptr(), *sfl, *margs, b, h, w, patch,
+            L.PM_OUTGOING if outgoing else 0)
+    return _record_call("raft_photo_metrics", head, (b, h, w, patch), flow.device, totals, want_map)
 
 
 def photo_errors(frame1, frame2, flow, mask=None, patch=7, outgoing=True, census_map=False):
@@ -623,21 +614,17 @@ def photo_errors(frame1, frame2, flow, mask=None, patch=7, outgoing=True, census
     ((h^2 + 1e-6)^0.45: ternary_loss's numerator); and census_map (float32 [B,1,H,W], h at every pixel, a
     confidence image) if asked for, else None.  Bitwise reproducible."""
     b, h, w = _check_photo_args("photo_errors", frame1, frame2, flow, mask, patch, outgoing)
-    _check_photo_devices("photo_errors", frame1, frame2, flow, mask)
     L = _lib()
     with torch.cuda.device(flow.device):
         record, cmap = _photo_metrics_call(frame1, frame2, flow, mask, patch, outgoing, b, h, w, None,
                                            bool(census_map))
-    sums = record.view(torch.float64)
-    nc = len(L.PM_COUNTS)
-    return PhotoErrors(*[record[:, i] for i in range(nc)], *[sums[:, nc + i] for i in range(len(L.PM_SUMS))], cmap)
+    return _record_tuple(PhotoErrors, L.PM_COUNTS, L.PM_SUMS, record, cmap)
 
 
 def photo_result(cnt, sums):
     """PhotoMetrics.result()'s dict from the totals' 16 slots read as integers (cnt) and as floats (sums)."""
     L = _lib()
-    c = dict(zip(L.PM_COUNTS, cnt))
-    s = {k: sums[len(L.PM_COUNTS) + i] for i, k in enumerate(L.PM_SUMS)}
+    c, s = _named_slots(L.PM_COUNTS, L.PM_SUMS, cnt, sums)
     nan = float("nan")
     tainted = c["n_nonfinite"] > 0
 
@@ -653,7 +640,7 @@ def photo_result(cnt, sums):
             "nonfinite": c["n_nonfinite"]}
 
 
-class PhotoMetrics:
+class PhotoMetrics(_RunningTotals):
     """Running label-free scores over a video or a dataset, kept on the device.
 
         m = PhotoMetrics()
@@ -669,23 +656,13 @@ class PhotoMetrics:
     def __init__(self, patch=7, outgoing=True):
         _check_photo_options("PhotoMetrics", patch, outgoing)
         self.patch, self.outgoing = patch, outgoing
-        self._totals = None
 
     def update(self, frame1, frame2, flow, mask=None):
         b, h, w = _check_photo_args("PhotoMetrics.update", frame1, frame2, flow, mask, self.patch, self.outgoing)
-        _check_photo_devices("PhotoMetrics.update", frame1, frame2, flow, mask)
-        if self._totals is not None and self._totals.device != flow.device:
-            raise RuntimeError(f"PhotoMetrics.update: the totals are on {self._totals.device}, flow on {flow.device}")
+        totals = self._totals_on("PhotoMetrics.update", flow)
         with torch.cuda.device(flow.device):
-            if self._totals is None:
-                self._totals = torch.zeros(_lib().PM_SLOTS, dtype=torch.int64, device=flow.device)
-            _photo_metrics_call(frame1, frame2, flow, mask, self.patch, self.outgoing, b, h, w, self._totals, False)
+            _photo_metrics_call(frame1, frame2, flow, mask, self.patch, self.outgoing, b, h, w, totals, False)
         return self
-
-    def reset(self):
-        """Clear the totals (no synchronisation)."""
-        if self._totals is not None:
-            self._totals.zero_()
 
     def result(self):
         """The totals as a dict (one device-to-host copy).  census = census_sum / (n_census + 1e-6), the
@@ -695,8 +672,4 @@ class PhotoMetrics:
         pixel; census_image_mean the mean over images (with a scored interior pixel) of census_sum / n_census;
         valid_share = n_valid / pixels; pixels, images, nonfinite the counts.  A mean over nothing is NaN (every
         key before the first update).  With nonfinite > 0 the means are NaN; valid_share stays a count's share."""
-        L = _lib()
-        if self._totals is None:
-            return photo_result([0] * L.PM_SLOTS, [0.0] * L.PM_SLOTS)
-        host = self._totals.cpu()
-        return photo_result(host.tolist(), host.view(torch.float64).tolist())
+        return photo_result(*self._host())

@@ -155,6 +155,34 @@ def test_block_sizes_and_grid_wrap():
     assert 32 * 32 == p and 25 * 41 == p + 1 and 513 * 512 > g * p
 
 
+@pytest.mark.parametrize("shape, partials", [((2, 513, 512), 256),   # the finalize stages one sample per pass
+                                             ((17, 3, 5), 1)])        # 16 samples per pass, then one alone
+def test_finalize_passes_with_totals(shape, partials):
+    """The finalize kernel's passes over the samples, with running totals: the records against the oracle, each
+    sample's record equal to that of the sample scored alone, and the totals equal to the records added in sample
+    order (the counts as integers, the sums in fp64, bit for bit)."""
+    from raft_optical_flow_amd import _lib as L
+    B, H, W = shape
+    assert L.load().raft_flow_metrics_ws_bytes(1, H, W) == partials * L.FM_SLOTS * 8 and partials <= G()
+    flow, gt, valid = R.metrics_case(*shape)
+    want = FM.metrics(flow, gt, valid)
+    args = (dev(flow), dev(gt), dev(valid))
+    totals = torch.zeros(L.FM_SLOTS, dtype=torch.int64, device=DEV)
+    recs, emap, raw = launch(*args, totals=totals)
+    check_sample_records(recs, want, f"{shape}")
+    check_map(emap, want)
+    for b in range(B):
+        assert np.array_equal(launch(*(a[b:b + 1] for a in args), epe_map=False)[2][0], raw[b]), b
+    tot = totals.cpu().numpy()
+    nc, ns = len(FM.COUNTS), len(FM.SUMS)
+    assert np.array_equal(tot[:nc], raw[:, :nc].sum(axis=0))                      # the counts: the records' sum
+    acc = np.zeros(ns)
+    for r in raw:                                                                 # the sums: added in sample order
+        acc = acc + r[nc:nc + ns].view(np.float64)
+    assert np.array_equal(tot[nc:nc + ns].view(np.float64), acc)
+    assert all(w["n"] > 0 for w in want) and unpack(tot)["images"] == B and unpack(tot)["reserved"] == 0
+
+
 def test_unpadded_view_with_odd_offset():
     """InputPadder.unpad's view of a padded flow, rows at an odd left offset, over a contiguous ground truth: the
     operands' alignments differ, nothing is copied, nothing outside the crop is read (the pad is NaN)."""

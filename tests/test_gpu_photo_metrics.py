@@ -258,6 +258,35 @@ def test_shapes_against_oracle(name):
             assert w["n_nonfinite"] == 0 and w["n_census"] > 0 and 0.5 < w["n_valid"] / w["pixels"] < 0.95
 
 
+def test_finalize_carries_sums_across_staging_runs_with_totals():
+    """Two samples of 257 tiles each, more than the finalize kernel stages at a time (256): each sample is staged
+    in two runs with its sums carried across.  The records against the oracle, each equal to that of the sample
+    scored alone, and the totals equal to the records added in sample order, bit for bit."""
+    lib = L()
+    shape = (2, lib.PM_TILE_H * 256 + 1, 3)
+    B, H, W = shape
+    tiles = -(-H // lib.PM_TILE_H) * -(-W // lib.PM_TILE_W)
+    assert tiles == 257 and lib.load().raft_photo_metrics_ws_bytes(1, H, W, 3) == tiles * lib.PM_SLOTS * 8
+    f1, f2, flow, mask = O.photo_case(*shape)
+    want = oracle(f1, f2, flow, mask, 3)
+    args = (dev(f1), dev(f2), dev(flow), dev(mask))
+    totals = torch.zeros(lib.PM_SLOTS, dtype=torch.int64, device=DEV)
+    recs, cmap, raw = launch(*args, patch=3, totals=totals)
+    check_sample_records(recs, want, f"{shape}")
+    check_map(cmap, want, f"{shape}")
+    assert all(w["n_census"] > 0 for w in want)
+    for b in range(B):
+        assert np.array_equal(launch(*(a[b:b + 1] for a in args), patch=3, census_map=False)[2][0], raw[b]), b
+    tot = totals.cpu().numpy()
+    nc, ns = len(O.COUNTS), len(O.SUMS)
+    assert np.array_equal(tot[:nc], raw[:, :nc].sum(axis=0))                      # the counts: the records' sum
+    acc = np.zeros(ns)
+    for r in raw:                                                                 # the sums: added in sample order
+        acc = acc + r[nc:nc + ns].view(np.float64)
+    assert np.array_equal(tot[nc:nc + ns].view(np.float64), acc)
+    assert unpack(tot)["images"] == B and unpack(tot)["reserved"] == [0, 0, 0, 0]
+
+
 @pytest.mark.parametrize("u8", [False, True])
 @pytest.mark.parametrize("patch", [3, 5, 7])
 def test_patches_and_frame_dtypes(patch, u8):
