@@ -201,10 +201,12 @@ class RAFT(nn.Module):
 
     def _plan_key(self, batch, height, width, iters, test_mode, flow_init, prec):
         # the stream layout knobs are read when a plan is built, so they are part of its key
+        # (every RAFT_* variable engine.py reads: tests/test_plan_key_host.py holds the two in step)
         knobs = (os.environ.get("RAFT_CTX_SIDE", "1"), os.environ.get("RAFT_FLOW_SIDE", "1"),
                  os.environ.get("RAFT_CONV_PAIR", "1"), os.environ.get("RAFT_FUSE_CONVF1", "1"),
                  os.environ.get("RAFT_FUSE_CONVC1", "1"), os.environ.get("RAFT_EPI_STATS", "1"),
-                 os.environ.get("RAFT_IN_NORM", "1"))
+                 os.environ.get("RAFT_IN_NORM", "1"), os.environ.get("RAFT_MERGE_FUSED", "1"),
+                 os.environ.get("RAFT_CTX_ORDER", "late"))
         guard = self.range_guard != "off"  # "off": no device-side checks either
         return (batch, height, width, iters, bool(test_mode), bool(self.args.alternate_corr), bool(flow_init), prec,
                 knobs, guard)
