@@ -802,6 +802,58 @@ int raft_splat_density(const float* flow, long batch_stride, long chan_stride, l
                        int H, int W, void* ws, float* density, raft_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Resizing frames and flows (utils.resize_frame, utils.resize_flow, utils.InputScaler):
+ * torch.nn.functional.interpolate's bilinear and area modes with exact integer coordinates.
+ * An additive entry: RAFT_HIP_ABI_VERSION stays 19.
+ * --------------------------------------------------------------------------- */
+/* dst = the Hs x Ws source resized to Hd x Wd, all B images and C channels in one launch.
+ *
+ * Definition.  Per axis, output index d of D samples over S source samples:
+ *   coordinate  align_corners off: n = max((2 d + 1) S - D, 0), den = 2 D   (the position
+ *               S / D * (d + 0.5) - 0.5, clamped at 0, as the exact ratio n / den);
+ *               align_corners on:  n = d (S - 1), den = max(D - 1, 1).
+ *               i0 = min(n / den, S - 1) (integer division), i1 = min(i0 + 1, S - 1),
+ *               lam = float(n % den) / float(den): both conversions are exact for D <= 2^23 and the
+ *               division is correctly rounded, so lam carries one rounding and no fp32 coordinate is ever
+ *               formed.  The integers are 64-bit wherever (2 d + 1) S can pass 2^31.
+ *               (x: taps x0, x1, weight lx; y: taps y0, y1, weight ly.)
+ *   bilinear    out = (1 - ly) * ((1 - lx) * v00 + lx * v01) + ly * ((1 - lx) * v10 + lx * v11)
+ *               in IEEE fp32, every written operation rounded to nearest once and nothing fused.  All four
+ *               taps are always read and blended: a NaN or Inf under a weight of 0 reaches the output, as
+ *               the formula says and as torch computes it.  With T = max |tap| and u = 2^-24, eight
+ *               roundings lie on the path of one output -- lx, 1 - lx, a product and the sum of the
+ *               horizontal blend (the errors of its two products are weighted by 1 - lx and lx and count
+ *               as one; the two horizontal blends are weighted by 1 - ly and ly likewise), then ly, 1 - ly,
+ *               a product and the sum of the vertical one: |out_fp32 - out_exact| <= ((1 + 4 u)^2 - 1) T,
+ *               8 u T to first order.
+ *   area        (RAFT_RESIZE_AREA: torch's mode="area", adaptive average pooling) out = the mean over
+ *               source rows floor(i Hs / Hd) .. ceil((i + 1) Hs / Hd) - 1 and the columns likewise: a
+ *               sequential fp32 sum in row-major order over the box, starting from 0, then one division
+ *               by the count (converted to fp32: exact below 2^24).  For a box of n samples
+ *               |out_fp32 - out_exact| <= (n + 1) u T to first order.
+ *   multipliers channel 0 is multiplied by mul0 and channel 1 by mul1 after the interpolation (one more
+ *               rounding each); the other channels are not.  A flow resized from Hs x Ws to Hd x Wd passes
+ *               mul0 = Wd / Ws and mul1 = Hd / Hs, each rounded to fp32 once on the host, so the vectors
+ *               stay in pixels of the new size; a plain frame passes 1.0 (exact).
+ *   uint8       uint8 taps are widened to float first.  A uint8 output is the value rounded to nearest
+ *               (ties to even) and saturated to 0..255 (NaN -> 0), as raft_warp_frame's is.
+ *
+ * Layout.  The source is, by src_dtype, RAFT_FRAME_F32_NCHW: float32, any C >= 1, unit element stride,
+ * element (b, c, y, x) at src[b * batch_stride + c * chan_stride + (top + y) * pitch + left + x] (strides
+ * in floats: a padded flow_up or an unpad view is read in place), or RAFT_FRAME_U8_NHWC: uint8
+ * [B][Hs][Ws][3], dense (strides and crop offsets are not read; C == 3).  dst is, by dst_dtype, float32
+ * [B][C][Hd][Wd] dense, or uint8 [B][Hd][Wd][3] dense (C == 3); all four combinations are supported.
+ * float32 pointers are 4-byte aligned; 16-byte (float32) and 4-byte (uint8) stores are used where the
+ * address allows.  Nothing outside the crop is read.  dst does not alias src.  B * C * Hs * Ws < 2^30 and
+ * B * C * Hd * Wd < 2^30.  Argument errors are reported before any launch. */
+#define RAFT_RESIZE_BILINEAR 0
+#define RAFT_RESIZE_AREA 1
+#define RAFT_RESIZE_ALIGN_CORNERS 1 /* flags bit 0: bilinear with align_corners (not with RAFT_RESIZE_AREA) */
+int raft_resize(const void* src, int src_dtype, long src_batch_stride, long src_chan_stride, long src_pitch,
+                int top, int left, int B, int C, int Hs, int Ws, void* dst, int dst_dtype, int Hd, int Wd, int mode,
+                int flags, float mul0, float mul1, raft_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Scoring a flow against ground truth (utils.flow_errors, utils.FlowMetrics): what evaluate.py's
  * validate_chairs / validate_sintel / validate_kitti compute on the host, on the device.
  * Additive entries: RAFT_HIP_ABI_VERSION stays 19.

@@ -42,6 +42,10 @@ VIZ_CLIP = 4   # clip both components to [0, clip_flow] first
 
 WARP_BORDER = 1   # raft_warp_frame flag: clamp the sampling position to the frame (default: zeros outside)
 
+RESIZE_BILINEAR = 0        # raft_resize modes
+RESIZE_AREA = 1            # torch's mode="area": adaptive average pooling
+RESIZE_ALIGN_CORNERS = 1   # raft_resize flag: bilinear with align_corners
+
 MASK_U8 = 0    # raft_flow_metrics mask tags: bool or uint8, valid where != 0
 MASK_F32 = 1   # float32, valid where >= 0.5
 
@@ -236,6 +240,8 @@ _PROTOS = {
                                 c_int, c_int, c_int, c_int, P, c_int, P, P]),
     "raft_splat_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "raft_splat_density": (c_int, [P, c_long, c_long, c_long, c_int, c_int, c_int, c_int, c_int, P, P, P]),
+    "raft_resize": (c_int, [P, c_int, c_long, c_long, c_long, c_int, c_int, c_int, c_int, c_int, c_int, P, c_int,
+                            c_int, c_int, c_int, c_int, c_float, c_float, P]),
     "raft_flow_metrics_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "raft_flow_metrics": (c_int, [P, c_long, c_long, c_long, P, c_long, c_long, c_long, P, c_int, c_long, c_long,
                                   c_int, c_int, c_int, c_float, P, P, P, P, P]),

@@ -36,6 +36,12 @@
                                                    soft_hamming, abs_robust_loss, create_outgoing_mask)
   PhotoMetrics         (the same)                  those sums accumulated over a video or a dataset without a copy or
                                                    a synchronisation per pair: "census", "ternary", "photo"
+  resize_frame         liteflownet3_util.py:227-232 F.interpolate(mode="bilinear" / "area") of a frame, float32 or
+                                                   uint8, with exact integer source coordinates (raft_resize)
+  resize_flow          liteflownet3_util.py:227-236 the same of a flow, its vectors scaled by the size ratio in the
+                                                   same launch (the reference's is_flow)
+  InputScaler          liteflownet3_util.py:121-241 fill: resize to a working size (next multiple of a stride, a given
+                                                   size, or a scale factor); unfill: back to the original size
 
 Every helper computes on the GPU through the HIP kernels of libraft_hip.so; a CPU tensor is
 copied to the current GPU and the result copied back (there is no host computation path).
@@ -360,6 +366,175 @@ def splat_density(flow):
         out = torch.empty(b, 1, h, w, device=fl.device)
         L.call("raft_splat_density", fl.data_ptr(), *sfl, 0, 0, b, h, w, ws.data_ptr(), out.data_ptr(), _stream())
     return out
+
+
+RESIZE_MODES = ("bilinear", "area")
+
+
+def check_size(name, size, what="size"):
+    """A target size as (h, w): two positive ints; raises otherwise."""
+    if isinstance(size, (str, bytes)) or not hasattr(size, "__len__") or len(size) != 2:
+        raise TypeError(f"{name}: {what} must be (height, width), got {size!r}")
+    for v in size:
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise TypeError(f"{name}: {what} must be two ints, got {size!r}")
+        if v < 1:
+            raise ValueError(f"{name}: {what} must be positive, got {size!r}")
+    return int(size[0]), int(size[1])
+
+
+def check_resize_mode(name, mode, align_corners=False):
+    """A resize mode and its align_corners: NotImplementedError for a mode that is not on the GPU path."""
+    if mode not in RESIZE_MODES:
+        raise NotImplementedError(f'{name}: only the modes "bilinear" and "area" are implemented, got {mode!r}')
+    if not isinstance(align_corners, bool):
+        raise TypeError(f"{name}: align_corners must be a bool, got {type(align_corners).__name__}")
+    if align_corners and mode != "bilinear":
+        raise ValueError(f"{name}: align_corners is an option of the bilinear mode, not of {mode!r}")
+    return mode, align_corners
+
+
+def scaled_size(name, height, width, stride=None, size=None, scale_factor=1.0):
+    """InputScaler's size arithmetic (liteflownet3_util.py:158-167): the next multiple of `stride`, or `size` as
+    given, or int(H * scale_factor), int(W * scale_factor)."""
+    import math
+    if stride is not None:
+        if size is not None:
+            raise ValueError(f"{name}: only stride OR size can be provided, not both")
+        if isinstance(stride, bool) or not isinstance(stride, int):
+            raise TypeError(f"{name}: stride must be an int, got {type(stride).__name__}")
+        if stride < 1:
+            raise ValueError(f"{name}: stride must be positive, got {stride}")
+        return (int(math.ceil(float(height) / stride)) * stride, int(math.ceil(float(width) / stride)) * stride)
+    if size is not None:
+        return check_size(name, size)
+    if isinstance(scale_factor, bool) or not isinstance(scale_factor, (int, float)):
+        raise TypeError(f"{name}: scale_factor must be a number, got {type(scale_factor).__name__}")
+    if not (0.0 < float(scale_factor) < float("inf")):
+        raise ValueError(f"{name}: scale_factor must be positive and finite, got {scale_factor!r}")
+    h, w = int(height * scale_factor), int(width * scale_factor)
+    if h < 1 or w < 1:
+        raise ValueError(f"{name}: scale_factor {scale_factor!r} leaves nothing of a {height} x {width} frame")
+    return h, w
+
+
+def _resize(name, frame, size, mode, align_corners, out_dtype, flow):
+    """resize_frame / resize_flow after their own checks of `frame`: one raft_resize launch on frame's device.
+    flow: channels 0 and 1 are multiplied by w / W and h / H (each ratio rounded to fp32 once)."""
+    L = _lib()
+    hd, wd = check_size(name, size)
+    mode, align_corners = check_resize_mode(name, mode, align_corners)
+    in_u8, out_u8 = frame.dtype == torch.uint8, out_dtype == torch.uint8
+    if in_u8:
+        b, c, hs, ws = frame.shape[0], 3, frame.shape[1], frame.shape[2]
+    else:
+        b, c, hs, ws = frame.shape
+    if b * c * hs * ws >= 1 << 30 or b * c * hd * wd >= 1 << 30:
+        raise ValueError(f"{name}: {b} x {c} x {hs} x {ws} -> {hd} x {wd} exceeds 2^30 elements")
+    with torch.cuda.device(frame.device):
+        if in_u8:
+            fr, sfr = frame.contiguous(), (0, 0, 0)
+        else:
+            fr, sfr = _pitched(frame, hs, ws)
+        out = torch.empty((b, hd, wd, 3) if out_u8 else (b, c, hd, wd), dtype=out_dtype, device=frame.device)
+        mul = (float(wd) / ws, float(hd) / hs) if flow else (1.0, 1.0)
+        L.call("raft_resize", fr.data_ptr(), L.FRAME_U8_NHWC if in_u8 else L.FRAME_F32_NCHW, *sfr, 0, 0, b, c, hs, ws,
+               out.data_ptr(), L.FRAME_U8_NHWC if out_u8 else L.FRAME_F32_NCHW, hd, wd,
+               L.RESIZE_AREA if mode == "area" else L.RESIZE_BILINEAR,
+               L.RESIZE_ALIGN_CORNERS if align_corners else 0, *mul, _stream())
+    return out
+
+
+def resize_frame(frame, size, mode="bilinear", align_corners=False, out_dtype=None):
+    """A frame at another size (raft_resize, one launch): torch.nn.functional.interpolate(frame, size, mode=mode,
+    align_corners=align_corners) with exact source coordinates.
+
+    frame is float32 [B,C,H,W] (any C >= 1; a crop of a larger tensor is read in place) or uint8 [B,H,W,3], on a
+    GPU; size = (h, w).  mode="bilinear": the source index and the weight of every output sample come out of
+    integer arithmetic, so the weight carries one rounding whatever the frame's size (torch forms the coordinate
+    in fp32: near column 1900 that costs up to 0.05 on values in 0..255); the blend is IEEE fp32, not fused, and
+    every tap is blended, so NaN / Inf spread as in torch.  mode="area": the mean over each output sample's box
+    of source samples (adaptive average pooling), summed in fp32 in row-major order; align_corners is a bilinear
+    option.  Returns float32 [B,C,h,w] or uint8 [B,h,w,3] (rounded to nearest even and saturated; C must be 3):
+    the frame's own dtype and layout, or out_dtype's.  Runs on the frame's device and current stream without
+    synchronising.  include/raft_hip.h has the definition."""
+    if not torch.is_tensor(frame):
+        raise TypeError(f"resize_frame: frame must be a tensor, got {type(frame).__name__}")
+    if frame.dtype not in (torch.float32, torch.uint8):
+        raise TypeError(f"resize_frame: frame must be float32 [B,C,H,W] or uint8 [B,H,W,3], got {frame.dtype}")
+    if out_dtype is None:
+        out_dtype = frame.dtype
+    if out_dtype not in (torch.float32, torch.uint8):
+        raise TypeError(f"resize_frame: out_dtype must be None, torch.float32 or torch.uint8, got {out_dtype!r}")
+    if frame.dim() != 4 or frame.numel() == 0:
+        raise ValueError(f"resize_frame: frame must be float32 [B, C, H, W] or uint8 [B, H, W, 3], got "
+                         f"{tuple(frame.shape)}")
+    if frame.dtype == torch.uint8 and frame.shape[3] != 3:
+        raise ValueError(f"resize_frame: a uint8 frame is [B, H, W, 3], got {tuple(frame.shape)}")
+    if out_dtype == torch.uint8 and frame.dtype != torch.uint8 and frame.shape[1] != 3:
+        raise ValueError(f"resize_frame: a uint8 result needs 3 channels, the frame has {frame.shape[1]}")
+    check_size("resize_frame", size)
+    check_resize_mode("resize_frame", mode, align_corners)
+    _check_devices("resize_frame", "frame", frame=frame)
+    return _resize("resize_frame", frame, size, mode, align_corners, out_dtype, False)
+
+
+def resize_flow(flow, size, mode="bilinear", align_corners=False):
+    """A flow at another size, in that size's pixels (raft_resize, one launch): resize_frame(flow, size, ...) with
+    channel 0 (x) multiplied by w / W and channel 1 (y) by h / H in the same launch, each ratio rounded to fp32
+    once: the reference's InputScaler with is_flow.  flow is float32 [B,2,H,W] on a GPU, any strides (a padded
+    flow_up or InputPadder.unpad's view is read in place); returns float32 [B,2,h,w]."""
+    _check_flow("resize_flow", flow)
+    check_size("resize_flow", size)
+    check_resize_mode("resize_flow", mode, align_corners)
+    _check_devices("resize_flow", flow=flow)
+    return _resize("resize_flow", flow, size, mode, align_corners, torch.float32, True)
+
+
+class InputScaler:
+    """Scale (..., C, H, W) tensors to a working size and back: the reference's InputScaler, on the GPU.
+
+        scaler = InputScaler(frame.shape, size=(544, 960))
+        flow = scaler.unfill(model(scaler.fill(image1), scaler.fill(image2))[-1], is_flow=True)
+
+    The working size is the next multiple of `stride`, or `size` as given, or int(H * scale_factor),
+    int(W * scale_factor).  fill resizes to it and unfill back to orig_shape's size, both through raft_resize
+    (resize_frame's arithmetic); with is_flow channels 0 and 1 are multiplied by the width and height ratios.
+    interpolation_mode is "bilinear" or "area" (anything else raises NotImplementedError).  A CPU tensor goes to
+    the current GPU and the result comes back; the result has the input's dtype."""
+
+    def __init__(self, orig_shape, stride=None, size=None, scale_factor=1.0, interpolation_mode="bilinear",
+                 interpolation_align_corners=False):
+        if len(orig_shape) < 2:
+            raise ValueError(f"InputScaler: orig_shape must end in (H, W), got {tuple(orig_shape)}")
+        self.orig_height, self.orig_width = check_size("InputScaler", tuple(int(v) for v in orig_shape[-2:]),
+                                                       "orig_shape")
+        self.interpolation_mode, self.interpolation_align_corners = check_resize_mode(
+            "InputScaler", interpolation_mode, interpolation_align_corners)
+        self.tgt_height, self.tgt_width = scaled_size("InputScaler", self.orig_height, self.orig_width, stride, size,
+                                                      scale_factor)
+
+    def fill(self, x, is_flow=False):
+        """x at the working size."""
+        return self._scale_keep_dims(x, (self.tgt_height, self.tgt_width), is_flow)
+
+    def unfill(self, x, is_flow=False):
+        """x back at the original size."""
+        return self._scale_keep_dims(x, (self.orig_height, self.orig_width), is_flow)
+
+    def _scale_keep_dims(self, x, size, is_flow):
+        if not torch.is_tensor(x):
+            raise TypeError(f"InputScaler: x must be a tensor, got {type(x).__name__}")
+        if x.dim() < 3 or x.numel() == 0 or not x.is_floating_point():
+            raise ValueError(f"InputScaler: x must be a floating-point (..., C, H, W) tensor, got {x.dtype} "
+                             f"{tuple(x.shape)}")
+        if is_flow and x.shape[-3] < 2:
+            raise ValueError(f"InputScaler: a flow has at least 2 channels, got {tuple(x.shape)}")
+        g = _on_gpu(x.detach()).float()
+        g = g.reshape(-1, *x.shape[-3:])
+        out = _resize("InputScaler", g, size, self.interpolation_mode, self.interpolation_align_corners,
+                      torch.float32, bool(is_flow))
+        return out.view(*x.shape[:-2], *size).to(device=x.device, dtype=x.dtype)
 
 
 FlowErrors = collections.namedtuple(
